@@ -3,12 +3,23 @@
 
 A step = one gpk_decode_batch over one per-GPU batch already resident in HBM
 (BASELINE.json configs[2], "C3": 64 M synthetic 1500 B Eth/IPv4/TCP packets,
-full TCP/IP checksum + flow hash). Secondary configs C2 (64 B UDP, IPv4
-checksum) and C4 (IMIX + VLAN + IPv6, all checksums and hashes) are measured
-in the same run and reported under "configs".
+full TCP/IP checksum + flow hash). A plain run sets that batch up, warms up,
+times the K steps and prints the result line; nothing else.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+--dump-outputs DIR writes what the last timed step computed (a fixed sample of
+its records, error arguments and flow hashes) as DIR/<name>.npy; the inputs are
+the same from run to run, so two builds can be compared output for output.
+
+--full adds everything else the line can carry: the secondary configs C2 (64 B
+UDP, IPv4 checksum), C4 (IMIX + VLAN + IPv6, all checksums and hashes) and C1
+under "configs", sampled and every-packet parity against the oracle, the
+narrow-record timing, the streaming-read and skeleton probes, the layer-fields
+row, the PCIe-inclusive row, C5 (pcapng replay) and the CPU baseline, each with
+its own --no-... switch as before. --bpf, --flows and --afpacket add their rows
+to a --full run.
 
 Multi-GPU: every rank generates and decodes its own shard (packets
 [rank*n, (rank+1)*n)); no collective on the data path ("scaling": "weak").
@@ -216,7 +227,7 @@ def probe_read(data, nbytes, steps, stream):
 
 
 def run_config(name, n, steps, warmup, rank, world, ctx, check_sample=2048, probe=False, full_check=False,
-               narrow=True):
+               narrow=True, dump=None):
     import torch
     from gopacket_amd import engine, shard, synth
     cfg = CONFIGS[name]
@@ -280,6 +291,8 @@ def run_config(name, n, steps, warmup, rank, world, ctx, check_sample=2048, prob
     # the slowest rank's kernel time (each rank's own, for the record)
     kernel_ms = shard.max_over_ranks(kernel_ms_own, world, device="cuda")
     kernel_ms_ranks = gather_ranks(kernel_ms_own, world)
+    if dump and rank == 0:
+        dump_outputs(dump, rec, err, fl, n)
 
     # the same decode with the 8-byte record (gpk_decode_batch_narrow, include/gpk.h gpk_record8), timed
     # the same way on its own outputs; the every-packet check below covers both forms
@@ -338,6 +351,36 @@ def run_config(name, n, steps, warmup, rank, world, ctx, check_sample=2048, prob
         del rec8, wide, err8, fl8
     torch.cuda.empty_cache()
     return res
+
+
+DUMP_PACKETS = 1 << 18  # 176 B per packet as written below: 46 MB
+
+
+def dump_outputs(path, rec, err, fl, n):
+    """--dump-outputs: what the last timed decode_device wrote, as .npy files
+    under `path`. Of a batch of more than DUMP_PACKETS packets a fixed sample
+    is written: packets 0 and n-1 and DUMP_PACKETS indices drawn with
+    numpy's default_rng(20), duplicates dropped, in ascending order; row r of
+    every file is the r-th of them. The outputs are bit patterns (status bits,
+    checksums, hashes), so they are written byte by byte, every value exact:
+      records.npy   float32 [k, 16]  the bytes of each 16-byte record
+      err_args.npy  float64 [k, 2]   the two u32 error arguments
+      flows.npy     float32 [k, 24]  the bytes of the link, network and
+                                     transport flow hashes (3 x u64, little
+                                     endian); only with the flow output on"""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    if n > DUMP_PACKETS:
+        rng = np.random.default_rng(20)
+        idx = np.unique(np.concatenate([rng.integers(0, n, DUMP_PACKETS), [0, n - 1]])).astype(np.int64)
+    else:
+        idx = np.arange(n, dtype=np.int64)
+    ti = torch.from_numpy(idx).cuda()
+    np.save(os.path.join(path, "records.npy"), rec.view(n, 16)[ti].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "err_args.npy"), err.view(n, 2)[ti].cpu().numpy().view(np.uint32).astype(np.float64))
+    if fl is not None:
+        f = torch.stack([fl[ti], fl[n + ti], fl[2 * n + ti]], dim=1).cpu().numpy()
+        np.save(os.path.join(path, "flows.npy"), f.view(np.uint8).reshape(len(idx), 24).astype(np.float32))
 
 
 # Bytes a decode writes per packet, and whether it streams the packet bytes
@@ -1313,8 +1356,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--packets", type=int, default=64 * 2**20, help="packets per GPU")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the headline config's last outputs (rank 0's; a fixed sample "
+                         "of a large batch) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything besides the headline figure too: the secondary configs, parity "
+                         "against the oracle, narrow records, probes, fields, PCIe, C5, the CPU baseline (each with "
+                         "its own switch below)")
     ap.add_argument("--configs", default=None,
-                    help="first one is the headline (default c3,c2,c4,c1, plus c4s strong scaling when N > 1)")
+                    help="first one is the headline, the only one timed without --full (default c3,c2,c4,c1, plus "
+                         "c4s strong scaling when N > 1)")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -1330,10 +1381,11 @@ def main():
     ap.add_argument("--c5", type=float, default=10.0, metavar="GIB",
                     help="config C5: replay a GIB-GiB pcapng end to end (gpk_replay_file); 0 = skip")
     ap.add_argument("--afpacket", type=int, default=0, metavar="MPKTS",
-                    help="also drain MPKTS Mi packets from an emulated TPACKET_V3 ring (gpk_tpacket_pump)")
+                    help="with --full, also drain MPKTS Mi packets from an emulated TPACKET_V3 ring (gpk_tpacket_pump)")
     ap.add_argument("--flows", action="store_true",
-                    help="also time row (f)3: flow-keyed grouping of 64M C6 packets (gpk_group_batch)")
-    ap.add_argument("--bpf", action="store_true", help="also time row (f)4: classic BPF over 64M C4 packets")
+                    help="with --full, also time row (f)3: flow-keyed grouping of 64M C6 packets (gpk_group_batch)")
+    ap.add_argument("--bpf", action="store_true",
+                    help="with --full, also time row (f)4: classic BPF over 64M C4 packets")
     ap.add_argument("--no-fields", action="store_true",
                     help="skip the layer-fields row (64M C4 decode + fields in one launch vs two)")
     ap.add_argument("--tables", default="auto", choices=["auto", "global"],
@@ -1359,22 +1411,26 @@ def main():
     if args.tables == "global":
         from gopacket_amd import _lib
         ctx.set_table_mode(_lib.TABLES_GLOBAL)
+    full = args.full
     names = (args.configs or ("c3,c2,c4,c1" + (",c4s" if world > 1 else ""))).split(",")
+    if not full:  # a plain run: the headline config's timed steps and nothing else
+        names = names[:1]
     results = {}
     for name in names:
         results[name] = run_config(name, args.packets, args.steps, args.warmup, rank, world, ctx,
-                                   check_sample=0 if args.no_parity else 2048,
-                                   probe=not args.no_probe,
-                                   full_check=not (args.no_parity or args.no_full_parity),
-                                   narrow=not args.no_narrow)
+                                   check_sample=2048 if full and not args.no_parity else 0,
+                                   probe=full and not args.no_probe,
+                                   full_check=full and not (args.no_parity or args.no_full_parity),
+                                   narrow=full and not args.no_narrow,
+                                   dump=args.dump_outputs if name == names[0] else None)
     threads = host_cores()[0]
     # every rank runs the rows below its own shard at N > 1 (weak: its own 64M batch; C5: its byte range)
     fields_ranks = None
-    if not args.no_fields:
+    if full and not args.no_fields:
         fr = fields_bench(ctx, n=args.packets, first=rank * args.packets, threads=rank_threads())
         fields_ranks = gather_obj(dict(fr, rank=rank), world)
     c5 = None
-    if args.c5 > 0:
+    if full and args.c5 > 0:
         c5 = (c5_replay(ctx, gib=args.c5, cpu_threads=threads) if world == 1
               else c5_sharded(ctx, rank, world, gib=args.c5))
     if rank == 0:
@@ -1387,7 +1443,7 @@ def main():
         out = {
             "metric": "Mpkts/s device-resident Eth/IPv4/TCP decode+cksum+flow-hash; % HBM roofline",
             "value": round(value, 2), "unit": "Mpkts/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(r["wall_s"] / args.steps * 1e3, 4),
+            "warmup": args.warmup, "ms_per_step": round(r["wall_s"] / args.steps * 1e3, 4), "full": full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8",
             "data": "synthetic (deterministic splitmix64 per packet index, generated in HBM)",
             "config": {"workload": CONFIGS[head]["workload"], "packets_per_gpu": r["n"],
@@ -1428,7 +1484,7 @@ def main():
                            note="one batch split at byte-balanced cuts; kernel_ms/achieved: the slowest rank's "
                                 "shard (kernel_ms_ranks: every rank's)")
             out["configs"][name] = row
-        if args.pcie and world == 1:
+        if full and args.pcie and world == 1:
             out["pcie_inclusive"] = pcie_inclusive(head, ctx)
         if fields_ranks:
             out["fields"] = dict(fields_ranks[0])
@@ -1438,18 +1494,18 @@ def main():
                 out["fields"]["value_all_ranks"] = round(sum(f["value"] for f in fields_ranks), 2)
         if c5 is not None:
             out["c5"] = c5
-        if args.bpf and world == 1:
+        if full and args.bpf and world == 1:
             out["bpf"] = bpf_filter_bench(ctx)
-        if args.flows and world == 1:
+        if full and args.flows and world == 1:
             out["flows"] = flow_grouping(ctx)
-        if args.afpacket > 0 and world == 1:
+        if full and args.afpacket > 0 and world == 1:
             out["afpacket"] = afpacket_pump(ctx, packets=args.afpacket * 2**20)
             out["afpacket"]["c1_parser"] = afpacket_pump(ctx, packets=args.afpacket * 2**20, cfg_name="c1")
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(head, names, seconds=args.cpu_seconds)
         else:
             out["cpu_baseline"] = None
-            if world > 1:
+            if full and world > 1:
                 out["cpu_baseline_note"] = ("measured at N=1 only (BENCH line): at N>1 the ranks share the host "
                                             "cores, which the per-rank parity checks use")
         print(json.dumps(out))

@@ -68,7 +68,7 @@ def test_synthetic(gpu_ctx, synth_cfg, cfg_name):
     (2, "gpk::decode_kernel<true,false,true,false,5,7,4>"),  # 64-76 B: the dword-aligned 5-chunk kernel
     (4, "gpk::decode_sb_kernel<true,7,6,false>"),            # IMIX, mean 362 B: stream before the parse
     (3, "gpk::decode_kernel<true,false,true,false,6,6,16>"),  # 1500 B: the 80-VGPR 6-chunk kernel
-])
+], ids=["synth2-small", "synth4-stream", "synth3-big"])  # ids without "::", which pytest node ids split at
 def test_kernel_choice_by_mean_packet(gpu_ctx, synth_cfg, want):
     """A parser without IPv6 (Ethernet, IPv4, TCP, Payload) takes the kernel
     its batch's mean packet selects (GPK_MID_MAXMEAN = 256 B, big packets from

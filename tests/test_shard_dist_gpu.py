@@ -107,7 +107,7 @@ def test_bench_two_ranks_strong_and_weak():
     env = dict(os.environ, OMP_NUM_THREADS="4")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--dist-backend", "gloo",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--dist-backend", "gloo",
            "--same-device", "--configs", "c3,c4s", "--packets", str(1 << 20), "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline", "--c5", "0.03", "--no-probe"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=400)
@@ -151,7 +151,7 @@ def test_bench_rccl_world_one():
     scaling itself stays unmeasured here (one GPU per box)."""
     env = dict(os.environ, OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--force-dist",
+           "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "1", "--force-dist",
            "--configs", "c3,c2", "--packets", str(1 << 20), "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--c5", "0", "--no-full-parity"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=280)

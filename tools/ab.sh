@@ -13,7 +13,7 @@ for V in "$@"; do
     global) unset GPK_LIB_VARIANT; EXTRA="--tables global" ;;
     *) export GPK_LIB_VARIANT=$V ;;
   esac
-  timeout -k 10 300 python3 bench.py $EXTRA --no-cpu-baseline --no-parity --configs $CFGS --steps 10 --warmup 2 \
+  timeout -k 10 300 python3 bench.py --full $EXTRA --no-cpu-baseline --no-parity --configs $CFGS --steps 10 --warmup 2 \
     > $OUT/$V.json 2> $OUT/$V.err || { echo "variant $V failed"; exit 1; }
   python3 - "$OUT/$V.json" "$V" <<'PY'
 import json, sys

@@ -17,7 +17,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt_c3 -o kt -- python3 bench.py --configs c3 --no-cpu-baseline --c5 0 --no-fields --no-narrow --steps 10 --warmup 2 > $OUT/kt_c3_bench.json || exit 1
 BCFGS=$(echo $CFGS | tr , '\n' | grep -v '^c4f$' | grep -v 'n$' | paste -sd, -)
-B="bench.py --no-cpu-baseline --no-parity --no-narrow --c5 0 --configs $BCFGS"
+B="bench.py --full --no-cpu-baseline --no-parity --no-narrow --c5 0 --configs $BCFGS"
 timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d $OUT/kt -o kt -- python3 $B --steps 5 --warmup 1 > $OUT/kt_bench.json || exit 1
 P="--kernel-include-regex decode_(sb_|)kernel -f csv"
 for c in $(echo $CFGS | tr , ' '); do
