@@ -73,7 +73,8 @@ EXPORTS = (
     "gpk_parser_create", "gpk_parser_destroy", "gpk_parser_add_decoder", "gpk_parser_set_options",
     "gpk_parser_set_outputs", "gpk_parser_decoder_for", "gpk_parser_set_ethertype",
     "gpk_parser_set_ipprotocol", "gpk_parser_set_tcp_port", "gpk_parser_set_udp_port", "gpk_ctx_create",
-    "gpk_ctx_destroy", "gpk_ctx_set_table_mode", "gpk_stop", "gpk_decode_batch", "gpk_decode_batch_narrow", "gpk_decode_batch_fields",
+    "gpk_ctx_destroy", "gpk_ctx_set_table_mode", "gpk_stop", "gpk_decode_batch", "gpk_decode_batch_narrow",
+    "gpk_decode_batch_narrow_compact", "gpk_wide_collect", "gpk_decode_batch_fields",
     "gpk_extract_fields",
     "gpk_decode_kernel_name", "gpk_decode_occupancy", "gpk_diag_set_buffer", "gpk_decode_batch_host", "gpk_decode_batch_host_fields",
     "gpk_decoded_list",
@@ -225,6 +226,15 @@ class Results8(ctypes.Structure):
                 ("flows", ctypes.c_void_p)]
 
 
+WIDE_COUNT_STRIDE = 32  # GPK_WIDE_COUNT_STRIDE: u32 words between two shards' counters
+
+
+class WideList(ctypes.Structure):
+    """gpk_wide_list: the sharded list of widened records (gpk_decode_batch_narrow_compact)."""
+    _fields_ = [("index", ctypes.c_void_p), ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("nshards", ctypes.c_uint32), ("shard_cap", ctypes.c_uint32)]
+
+
 _lib = None
 
 
@@ -268,6 +278,8 @@ def lib():
         "gpk_stop": ([vp], c_int),
         "gpk_decode_batch": ([vp, vp, P(Batch), P(Results), vp], c_int),
         "gpk_decode_batch_narrow": ([vp, vp, P(Batch), P(Results8), vp], c_int),
+        "gpk_decode_batch_narrow_compact": ([vp, vp, P(Batch), P(Results8), P(WideList), vp], c_int),
+        "gpk_wide_collect": ([P(WideList), vp, vp, P(u64), P(u64)], c_int),
         "gpk_decode_batch_host": ([vp, vp, P(Batch), P(Results)], c_int),
         "gpk_decode_batch_host_fields": ([vp, vp, P(Batch), P(Results), vp], c_int),
         "gpk_extract_fields": ([P(Batch), vp, vp, vp], c_int),

@@ -79,6 +79,13 @@ struct KParams {
   // packet whose record does not fit writes its full one to wide[i] (gpk.h)
   uint32_t narrow;
   gpk_record* wide;
+  // narrow == 2 (gpk_decode_batch_narrow_compact): the full records go to a sharded list
+  // (gpk_wide_list, gpk.h) instead: wide is the list's records, block b appends to shard
+  // b & shard_mask, whose counter is wide_counts[shard * GPK_WIDE_COUNT_STRIDE]
+  uint32_t* wide_index;
+  uint32_t* wide_counts;
+  uint32_t shard_cap;
+  uint32_t shard_mask;
 };
 
 // Straight-line common-case parse (fast_parser below). Each bit says the

@@ -655,6 +655,10 @@ static int make_params(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, cons
   P.fields = nullptr;
   P.narrow = 0;
   P.wide = nullptr;
+  P.wide_index = nullptr;
+  P.wide_counts = nullptr;
+  P.shard_cap = 0;
+  P.shard_mask = 0;
   return GPK_OK;
 }
 
@@ -698,6 +702,78 @@ int gpk_decode_batch_narrow(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b,
   if (rc) return rc;
   HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, 0, s));
   return note_launch(c, slot, s);
+}
+
+#ifndef GPK_DIAG_WIDE_RESETS
+#define GPK_DIAG_WIDE_RESETS 1  // timing only: 2 enqueues the counter reset twice (what one reset costs a launch)
+#endif
+
+// nshards a power of two in 1..256, and the arrays the kernel appends to
+static bool wide_list_ok(const gpk_wide_list* l) {
+  if (!l || l->nshards < 1 || l->nshards > 256 || (l->nshards & (l->nshards - 1))) return false;
+  if (!l->counts || (l->shard_cap && (!l->index || !l->records))) return false;
+  return (uint64_t)l->nshards * l->shard_cap <= 0xffffffffull;
+}
+
+int gpk_decode_batch_narrow_compact(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results8* o8,
+                                    const gpk_wide_list* list, void* stream) {
+  if (!wide_list_ok(list) || ((uintptr_t)list->records & 15) != 0) return GPK_EINVAL;  // one dwordx4 store per entry
+  if (!o8 || !b || b->n > 0xffffffffull || (b->n && !o8->records)) return GPK_EINVAL;  // 32-bit packet indices
+  const gpk_results o{reinterpret_cast<gpk_record*>(o8->records), o8->err_args, o8->flows, nullptr};
+  gpk::KParams P;
+  int rc = make_params(c, p, b, &o, P);
+  if (rc) return rc;
+  P.narrow = 2;
+  P.wide = list->records;
+  P.wide_index = list->index;
+  P.wide_counts = list->counts;
+  P.shard_cap = list->shard_cap;
+  P.shard_mask = list->nshards - 1;
+  hipStream_t s = (hipStream_t)stream;
+  std::lock_guard<std::mutex> g(c->mu);
+  gpk::DeviceScope dscope(c->device);
+  HIPCHK(dscope.err);
+  int slot = 0;
+  rc = upload(c, p, P, &slot, s);
+  if (rc) return rc;
+  // the whole counter lines, so a list is reused without the caller clearing it
+  for (int k = 0; k < GPK_DIAG_WIDE_RESETS; k++)
+    HIPCHK(hipMemsetAsync(list->counts, 0, (size_t)list->nshards * GPK_WIDE_COUNT_STRIDE * sizeof(uint32_t), s));
+  HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, 0, s));
+  return note_launch(c, slot, s);
+}
+
+int gpk_wide_collect(const gpk_wide_list* l, uint32_t* out_index, gpk_record* out_records, uint64_t* stored,
+                     uint64_t* total) {
+  if (!wide_list_ok(l) || !stored || !total) return GPK_EINVAL;
+  uint64_t ns = 0, nt = 0;
+  for (uint32_t s = 0; s < l->nshards; s++) {
+    const uint32_t cnt = l->counts[(size_t)s * GPK_WIDE_COUNT_STRIDE];
+    nt += cnt;
+    ns += cnt < l->shard_cap ? cnt : l->shard_cap;
+  }
+  *stored = ns;
+  *total = nt;
+  if (!ns) return GPK_OK;
+  if (!out_index || !out_records) return GPK_EINVAL;
+  // positions of the stored entries, sorted by the packet index they hold
+  std::vector<uint32_t> pos;
+  try {
+    pos.reserve(ns);
+  } catch (const std::bad_alloc&) {
+    return GPK_ENOMEM;
+  }
+  for (uint32_t s = 0; s < l->nshards; s++) {
+    const uint32_t cnt = l->counts[(size_t)s * GPK_WIDE_COUNT_STRIDE];
+    const uint32_t m = cnt < l->shard_cap ? cnt : l->shard_cap;
+    for (uint32_t k = 0; k < m; k++) pos.push_back(s * l->shard_cap + k);
+  }
+  std::sort(pos.begin(), pos.end(), [l](uint32_t a, uint32_t b2) { return l->index[a] < l->index[b2]; });
+  for (uint64_t k = 0; k < ns; k++) {
+    out_index[k] = l->index[pos[k]];
+    out_records[k] = l->records[pos[k]];
+  }
+  return GPK_OK;
 }
 
 int gpk_decode_batch_fields(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results* o,

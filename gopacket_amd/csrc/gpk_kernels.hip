@@ -1294,7 +1294,39 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
       if (l4c == jexist || (udp && jexist == 0)) st |= GPK_ST_L4_VALID;
     }
   }
-  if (active && P.narrow) {
+  if (P.narrow == 2) {
+    // gpk_decode_batch_narrow_compact: the narrow record as below, the full
+    // records of the wave's widened packets appended to the block's shard of
+    // the list (gpk_wide_list, gpk.h). The whole wave is here (inactive lanes
+    // widen nothing): one ballot, one returning add of the wave's count on
+    // the shard's counter, and the widened lanes store to consecutive slots
+    // from the base it returned, so a wave's entries are contiguous. A slot at
+    // or above shard_cap is counted but not stored.
+    const bool widen = active && (q.nlayers > 8 || ((st & GPK_ST_IP4_CSUM) && !(st & GPK_ST_IP4_VALID)) ||
+                                  ((st & GPK_ST_L4_CSUM) && l4c != jexist));
+    if (active) {
+      const uint32_t st8 = (st & ~(GPK_ST_NLAYERS_MASK << GPK_ST_NLAYERS_SHIFT)) |
+                           ((q.nlayers > 8 ? GPK_ST8_NLAYERS_MASK : q.nlayers) << GPK_ST_NLAYERS_SHIFT) |
+                           (widen ? GPK_ST8_WIDE : 0u);
+      __builtin_nontemporal_store((uint64_t)st8 << 32 | lay_lo, reinterpret_cast<uint64_t*>(P.records) + i);
+    }
+    const uint64_t mask = __ballot(widen);
+    if (mask) {  // uniform over the wave
+      const uint32_t shard = (uint32_t)(i >> 8) & P.shard_mask;  // i / kBlock: the block, equal in every lane
+      uint32_t base = 0;
+      if (lane == 0)
+        base = __hip_atomic_fetch_add(P.wide_counts + shard * GPK_WIDE_COUNT_STRIDE, (uint32_t)__popcll(mask),
+                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      base = readlane32(base, 0);
+      const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32),
+                                                             __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+      if (widen && slot < P.shard_cap) {
+        const uint64_t e = (uint64_t)shard * P.shard_cap + slot;
+        __builtin_nontemporal_store((uint32_t)i, P.wide_index + e);
+        __builtin_nontemporal_store(u32x4{lay_lo, lay_hi, st, ip4c | (l4c << 16)}, reinterpret_cast<u32x4*>(P.wide) + e);
+      }
+    }
+  } else if (active && P.narrow) {
     // gpk_record8 (gpk.h): the full record only where Correct is not the
     // header's Checksum field (checksum.go:9-21; a UDP 0 is Valid unchecked,
     // udp.go:144-158) or the list has more than 8 entries

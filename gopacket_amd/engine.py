@@ -142,6 +142,23 @@ class Context:
                           flows.data_ptr() if flows is not None else None)
         check(lib().gpk_decode_batch_narrow(self.h, parser.h, ctypes.byref(b), ctypes.byref(r), _stream_ptr(stream)))
 
+    def decode_device_narrow_compact(self, parser, data, offsets, caplens, records8, wide_list, err_args=None,
+                                     flows=None, stream=None):
+        """gpk_decode_batch_narrow_compact: decode_device_narrow with the full
+        records of the widened packets appended to wide_list (a WideList)
+        instead of a 16-byte-per-packet side array. The library resets the
+        list's counters on `stream` first. Device tensors; enqueued on `stream`;
+        wide_list.collect() afterwards."""
+        n = offsets.numel()
+        if records8.numel() * records8.element_size() < 8 * n:
+            raise ValueError("records8 needs 8 bytes per packet")
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        r = _lib.Results8(records8.data_ptr(), None, err_args.data_ptr() if err_args is not None else None,
+                          flows.data_ptr() if flows is not None else None)
+        wl = wide_list.c_struct()
+        check(lib().gpk_decode_batch_narrow_compact(self.h, parser.h, ctypes.byref(b), ctypes.byref(r),
+                                                    ctypes.byref(wl), _stream_ptr(stream)))
+
     def extract_fields(self, data, offsets, caplens, layouts, fields, stream=None):
         """gpk_extract_fields: the layer fields (include/gpk.h gpk_fields, 128
         bytes per packet; FIELDS_DTYPE) of a device batch from the layouts a
@@ -319,6 +336,74 @@ class Context:
         pkt = bytes(pkt)
         check(lib().gpk_decoded_list_host(self.h, parser.h, pkt, len(pkt), out, cap, ctypes.byref(n)))
         return [out[i] for i in range(min(n.value, cap))]
+
+
+def wide_shard_cap(n, nshards):
+    """The shard_cap with which a gpk_wide_list of nshards shards cannot
+    overflow on n packets: every 256-packet block of a shard all widened."""
+    blocks = (int(n) + 255) // 256
+    return (blocks + nshards - 1) // nshards * 256
+
+
+def wide_collect(index, records, counts, nshards, shard_cap):
+    """gpk_wide_collect over host copies (numpy) of a list's three arrays:
+    (index sorted ascending, their records as RECORD_DTYPE, the counters' sum);
+    the sum exceeds len(index) when a shard overflowed."""
+    index = np.ascontiguousarray(index, dtype=np.uint32)
+    records = np.ascontiguousarray(records).view(np.uint8)
+    counts = np.ascontiguousarray(counts, dtype=np.uint32)
+    cap = nshards * shard_cap
+    out_i = np.zeros(max(cap, 1), np.uint32)
+    out_r = np.zeros(max(cap, 1), _lib.RECORD_DTYPE)
+    wl = _lib.WideList(index.ctypes.data if cap else None, records.ctypes.data if cap else None, counts.ctypes.data,
+                       nshards, shard_cap)
+    stored, total = ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib().gpk_wide_collect(ctypes.byref(wl), out_i.ctypes.data, out_r.ctypes.data, ctypes.byref(stored),
+                                 ctypes.byref(total)))
+    return out_i[:stored.value], out_r[:stored.value], total.value
+
+
+class WideList:
+    """gpk_wide_list in device memory: the compact sharded list that
+    Context.decode_device_narrow_compact appends the widened packets' full
+    records to. nshards: a power of two in 1..256; shard_cap: entries per shard
+    (never_overflows(n) is the capacity no batch of n packets can overflow; a
+    caller that knows its traffic's widening share sizes far below it and checks
+    collect()'s total against the stored entries)."""
+
+    def __init__(self, nshards, shard_cap, device="cuda"):
+        import torch
+        self.nshards, self.shard_cap = int(nshards), int(shard_cap)
+        cap = max(self.nshards * self.shard_cap, 1)
+        self.index = torch.zeros(cap, dtype=torch.int32, device=device)
+        self.records = torch.zeros(cap * 16, dtype=torch.uint8, device=device)
+        self.counts = torch.zeros(max(self.nshards, 1) * _lib.WIDE_COUNT_STRIDE, dtype=torch.int32, device=device)
+
+    def never_overflows(self, n):
+        return wide_shard_cap(n, self.nshards)
+
+    def nbytes(self):
+        """Device bytes the list holds."""
+        return sum(t.numel() * t.element_size() for t in (self.index, self.records, self.counts))
+
+    def c_struct(self):
+        return _lib.WideList(self.index.data_ptr(), self.records.data_ptr(), self.counts.data_ptr(), self.nshards,
+                             self.shard_cap)
+
+    def collect(self):
+        """After the decode: synchronises, copies the list back and returns
+        (index, records, total): the stored entries sorted by packet index
+        (uint32, RECORD_DTYPE) and the number of widened packets; total >
+        len(index) says a shard overflowed and those packets are not stored."""
+        import torch
+        torch.cuda.synchronize(self.index.device)
+        counts = self.counts.cpu().numpy().view(np.uint32)
+        # only the filled head of every shard crosses the bus: the copies are a list of capacity `hi`
+        s, cap = self.nshards, self.shard_cap
+        hi = min(int(counts[::_lib.WIDE_COUNT_STRIDE].max()), cap)
+        idx = self.index[:s * cap].view(s, cap)[:, :hi].contiguous().cpu().numpy().view(np.uint32)
+        rec = self.records[:s * cap * 16].view(s, cap * 16)[:, :hi * 16].contiguous().cpu().numpy()
+        return wide_collect(idx.reshape(-1), rec.reshape(-1), counts, s, hi)
 
 
 def _batch_of(data, offsets, caplens):

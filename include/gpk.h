@@ -32,6 +32,9 @@
  *                                          (pcap/afpacket sources hand over host buffers)
  *   gpk_decode_batch_narrow                gpk_decode_batch with an 8-byte record per packet (the
  *                                          full one only where it does not fit, gpk_record8)
+ *   gpk_decode_batch_narrow_compact        the same with the full records of those packets in a
+ *                                          compact sharded list (gpk_wide_list) instead of wide[n]
+ *   gpk_wide_collect                       host side: a copied-back gpk_wide_list sorted by packet
  *   gpk_decode_batch_fields                gpk_decode_batch plus gpk_extract_fields in one launch
  *   gpk_extract_fields                     the scalar fields the six decoders' DecodeFromBytes set
  *                                          on their structs (layers/ethernet.go:42-55,
@@ -230,6 +233,37 @@ static inline unsigned gpk_record8_nlayers(const gpk_record8* r) {
   return (r->status >> GPK_ST_NLAYERS_SHIFT) & GPK_ST8_NLAYERS_MASK;
 }
 
+/* ---- compact list of the widened records (gpk_decode_batch_narrow_compact) --
+ * wide[n] costs 16 bytes of device memory per packet although only the few
+ * packets with GPK_ST8_WIDE write to it, each with a scattered 16-byte store.
+ * The list holds only those packets: entry = {packet index, full gpk_record},
+ * appended by the decode kernel. It is cut into nshards independent segments
+ * of shard_cap entries, each with its own counter on its own 128-byte line
+ * (one counter for the whole batch would serialise every wave's append on one
+ * word); the 256-packet block b = i / 256 appends to shard b & (nshards - 1),
+ * so blocks that run at the same time spread over all counters. A wave draws
+ * one run of slots for all its widened packets: their stores are contiguous.
+ * After the call shard s occupies entries [s * shard_cap, s * shard_cap +
+ * min(counts[s * GPK_WIDE_COUNT_STRIDE], shard_cap)) of index and records, in
+ * unspecified order inside the shard (gpk_wide_collect sorts a host copy).
+ * Overflow: a widened packet whose slot is at or above shard_cap is counted
+ * but not stored, and nothing is ever written outside a shard's segment; the
+ * caller sees counts > shard_cap and reruns with a larger list or with
+ * gpk_decode_batch_narrow. shard_cap = ceil(ceil(n / 256) / nshards) * 256
+ * can never overflow (every block of a shard all widened); a caller who knows
+ * the widening share of its traffic can size far below that. */
+#define GPK_WIDE_COUNT_STRIDE 32   /* u32 words between two shards' counters: one 128-byte line each */
+
+typedef struct gpk_wide_list {
+  uint32_t* index;     /* [nshards * shard_cap]  packet index of each entry                       */
+  gpk_record* records; /* [nshards * shard_cap]  its full record; 16-byte aligned                 */
+  uint32_t* counts;    /* [nshards * GPK_WIDE_COUNT_STRIDE]; word 0 of each line: the number of
+                          widened packets that drew a slot in that shard, INCLUDING those beyond
+                          shard_cap (which are not stored)                                        */
+  uint32_t nshards;    /* power of two, 1..256                                                    */
+  uint32_t shard_cap;  /* entries per shard; may be 0 (count only)                                */
+} gpk_wide_list;
+
 /* ---- optional per-packet layout (64 B): where each layer struct points ----
  * For every DecodingLayer implementation (slot = kind-1, Payload and Fragment
  * share slot 7) the byte range [start, end) — relative to the packet start —
@@ -423,6 +457,27 @@ int gpk_decode_batch(gpk_ctx* ctx, const gpk_parser* p, const gpk_batch* batch,
  * layouts. The results are exactly gpk_decode_batch's, in the narrow form. */
 int gpk_decode_batch_narrow(gpk_ctx* ctx, const gpk_parser* p, const gpk_batch* batch,
                             const gpk_results8* out, void* stream);
+
+/* gpk_decode_batch_narrow with the widened packets' full records in a compact
+ * sharded list (gpk_wide_list above; device memory) instead of wide[n]:
+ * records, err_args and flows are exactly gpk_decode_batch_narrow's, and every
+ * packet with GPK_ST8_WIDE has exactly one entry {i, the record
+ * gpk_decode_batch_narrow writes to wide[i]} in shard (i / 256) & (nshards - 1),
+ * unless that shard overflowed. out->wide is ignored and may be NULL. The
+ * counters are reset on `stream` before the launch, so a list is reused
+ * without the caller clearing it. GPK_EINVAL, before anything is enqueued and
+ * whatever batch->n: nshards not a power of two in 1..256, counts NULL, index
+ * or records NULL with shard_cap > 0, records not 16-byte aligned, nshards *
+ * shard_cap >= 2^32, batch->n >= 2^32 (the indices are 32-bit). */
+int gpk_decode_batch_narrow_compact(gpk_ctx* ctx, const gpk_parser* p, const gpk_batch* batch,
+                                    const gpk_results8* out /* out->wide ignored, may be NULL */,
+                                    const gpk_wide_list* list, void* stream);
+
+/* From host copies of a list's three arrays: the stored entries of all shards sorted by packet
+ * index into out_index / out_records (room for nshards*shard_cap), their number in *stored, the
+ * sum of the counters in *total (total > stored: the list overflowed). No GPU call. */
+int gpk_wide_collect(const gpk_wide_list* host_copy, uint32_t* out_index, gpk_record* out_records,
+                     uint64_t* stored, uint64_t* total);
 
 /* Layer fields of every packet of a device batch from the layouts a
  * gpk_decode_batch with layouts wrote for it (device memory; fields[n] device
