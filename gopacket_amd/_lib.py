@@ -99,6 +99,8 @@ EXPORTS = (
     "gpk_grouper_create", "gpk_grouper_destroy", "gpk_group_batch", "gpk_pack_batch", "gpk_decode_group_batch",
     # include/gpk_bpf.h
     "gpk_bpf_create", "gpk_bpf_destroy", "gpk_bpf_run", "gpk_bpf_select",
+    # include/gpk_defrag.h
+    "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -113,6 +115,19 @@ GROUP_NONE, GROUP_USELESS, GROUP_FRAG_TOO_SMALL, GROUP_FRAG_OFFSET, GROUP_FRAG_O
 class Groups(ctypes.Structure):
     _fields_ = [("group_of", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("start", ctypes.c_void_p),
                 ("first", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+# include/gpk_defrag.h constants
+DEFRAG_HELD, DEFRAG_EHOLE, DEFRAG_EINVALID, DEFRAG_EMAXLEN, DEFRAG_EPANIC = -16, -17, -18, -19, -20
+DEFRAG_MAX_LIST = 8192
+
+
+class Datagrams(ctypes.Structure):
+    """gpk_datagrams: the outputs of gpk_defrag_batch (device arrays)."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("last", ctypes.c_void_p), ("length", ctypes.c_void_p),
+                ("offsets", ctypes.c_void_p), ("caplens", ctypes.c_void_p), ("payload_off", ctypes.c_void_p),
+                ("pending", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("data", ctypes.c_void_p),
+                ("data_cap", ctypes.c_uint64)]
 
 # include/gpk_afpacket.h constants
 TPACKET_V1, TPACKET_V2, TPACKET_V3, TPACKET_HIGHEST = 0, 1, 2, -1
@@ -352,6 +367,9 @@ def lib():
         "gpk_group_batch": ([vp, P(Batch), P(Results), c_int, u32, P(Groups), vp], c_int),
         "gpk_pack_batch": ([P(Batch), vp, u64, vp, vp, vp, vp], c_int),
         "gpk_decode_group_batch": ([vp, vp, P(Batch), P(Results), vp, c_int, P(Groups), vp], c_int),
+        "gpk_defragger_create": ([P(vp), c_int, u64], c_int),
+        "gpk_defragger_destroy": ([vp], c_int),
+        "gpk_defrag_batch": ([vp, P(Batch), P(Results), P(Groups), P(Datagrams), vp], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),
