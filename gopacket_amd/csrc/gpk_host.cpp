@@ -667,20 +667,41 @@ int gpk_diag_set_buffer(void* buf) {
   return GPK_OK;
 }
 
+}  // extern "C"
+
+// The tail of every decode entry point, under the context's lock and on its
+// device: parser p's tables for a launch on stream s (upload, which fills the
+// table fields of P), the caller's enqueue step (a status, 0 to go on), then
+// the slot's completion mark (note_launch). mark = false: the step only
+// describes the launch (kernel name, occupancy); its result is returned as is.
+template <class F>
+static int with_tables(gpk_ctx* c, const gpk_parser* p, gpk::KParams& P, hipStream_t s, bool mark, F step) {
+  std::lock_guard<std::mutex> g(c->mu);
+  gpk::DeviceScope dscope(c->device);
+  HIPCHK(dscope.err);
+  int slot = 0;
+  int rc = upload(c, p, P, &slot, s);
+  if (rc) return rc;
+  rc = step();
+  if (rc || !mark) return rc;
+  return note_launch(c, slot, s);
+}
+// ... for the plain decode launch
+static int launch_decode(gpk_ctx* c, const gpk_parser* p, gpk::KParams& P, bool layouts, hipStream_t s) {
+  return with_tables(c, p, P, s, true, [&]() -> int {
+    HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, layouts, s));
+    return GPK_OK;
+  });
+}
+
+extern "C" {
+
 int gpk_decode_batch(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results* o, void* stream) {
   if (!o) return GPK_EINVAL;
   gpk::KParams P;
   int rc = make_params(c, p, b, o, P);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, o->layouts != nullptr, s));
-  return note_launch(c, slot, s);
+  return launch_decode(c, p, P, o->layouts != nullptr, (hipStream_t)stream);
 }
 
 int gpk_decode_batch_narrow(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results8* o8,
@@ -693,20 +714,8 @@ int gpk_decode_batch_narrow(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b,
   if (rc) return rc;
   P.narrow = 1;
   P.wide = o8->wide;
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, 0, s));
-  return note_launch(c, slot, s);
+  return launch_decode(c, p, P, false, (hipStream_t)stream);
 }
-
-#ifndef GPK_DIAG_WIDE_RESETS
-#define GPK_DIAG_WIDE_RESETS 1  // timing only: 2 enqueues the counter reset twice (what one reset costs a launch)
-#endif
 
 // nshards a power of two in 1..256, and the arrays the kernel appends to
 static bool wide_list_ok(const gpk_wide_list* l) {
@@ -730,17 +739,12 @@ int gpk_decode_batch_narrow_compact(gpk_ctx* c, const gpk_parser* p, const gpk_b
   P.shard_cap = list->shard_cap;
   P.shard_mask = list->nshards - 1;
   hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  // the whole counter lines, so a list is reused without the caller clearing it
-  for (int k = 0; k < GPK_DIAG_WIDE_RESETS; k++)
+  return with_tables(c, p, P, s, true, [&]() -> int {
+    // the whole counter lines, so a list is reused without the caller clearing it
     HIPCHK(hipMemsetAsync(list->counts, 0, (size_t)list->nshards * GPK_WIDE_COUNT_STRIDE * sizeof(uint32_t), s));
-  HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, 0, s));
-  return note_launch(c, slot, s);
+    HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, 0, s));
+    return GPK_OK;
+  });
 }
 
 int gpk_wide_collect(const gpk_wide_list* l, uint32_t* out_index, gpk_record* out_records, uint64_t* stored,
@@ -788,14 +792,10 @@ int gpk_decode_batch_fields(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b,
   if (rc) return rc;
   P.fields = fields;
   hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  HIPCHK(gpk_launch_decode_fields(&P, s, nullptr));
-  return note_launch(c, slot, s);
+  return with_tables(c, p, P, s, true, [&]() -> int {
+    HIPCHK(gpk_launch_decode_fields(&P, s, nullptr));
+    return GPK_OK;
+  });
 }
 
 // gpk_decode_batch for the library's own pipelines (gpk_replay_file,
@@ -815,23 +815,20 @@ extern "C" __attribute__((visibility("hidden"))) int gpk_decode_batch_ex(gpk_ctx
   if (rc) return rc;
   P.fields = fields;
   hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  if (kname && kcap) {
+  return with_tables(c, p, P, s, true, [&]() -> int {
+    const int l4 = (p->outputs & GPK_OUT_L4_CSUM) != 0, layouts = o->layouts != nullptr;
+    if (kname && kcap) {
+      if (fields)
+        gpk_launch_describe_fields(&P, kname, kcap);
+      else
+        gpk_launch_describe(&P, l4, layouts, kname, kcap);
+    }
     if (fields)
-      gpk_launch_describe_fields(&P, kname, kcap);
+      HIPCHK(gpk_launch_decode_fields(&P, s, nullptr));
     else
-      gpk_launch_describe(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, o->layouts != nullptr, kname, kcap);
-  }
-  if (fields)
-    HIPCHK(gpk_launch_decode_fields(&P, s, nullptr));
-  else
-    HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, o->layouts != nullptr, s));
-  return note_launch(c, slot, s);
+      HIPCHK(gpk_launch_decode(&P, l4, layouts, s));
+    return GPK_OK;
+  });
 }
 
 // gpk_decode_batch plus the fused grouping key per packet (gpk_flows.hip
@@ -848,33 +845,19 @@ extern "C" __attribute__((visibility("hidden"))) int gpk_decode_batch_keys(gpk_c
   P.keys = keys;
   P.khash = khash;
   P.kcode = kcode;
-  hipStream_t s = (hipStream_t)stream;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, s);
-  if (rc) return rc;
-  HIPCHK(gpk_launch_decode(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, o->layouts != nullptr, s));
-  return note_launch(c, slot, s);
+  return launch_decode(c, p, P, o->layouts != nullptr, (hipStream_t)stream);
 }
 
 int gpk_decode_kernel_name(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, int with_layouts, char* buf,
                            size_t cap) {
   if (!buf || !cap) return GPK_EINVAL;
   gpk::KParams P;
-  gpk_results o{nullptr, nullptr, nullptr, nullptr};
   int rc = make_params(c, p, b, nullptr, P);
   if (rc) return rc;
-  (void)o;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, c->stream);
-  if (rc) return rc;
-  if (with_layouts == GPK_NAME_FIELDS) return gpk_launch_describe_fields(&P, buf, cap);
-  return gpk_launch_describe(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, with_layouts != 0, buf, cap);
+  return with_tables(c, p, P, c->stream, false, [&]() -> int {
+    if (with_layouts == GPK_NAME_FIELDS) return gpk_launch_describe_fields(&P, buf, cap);
+    return gpk_launch_describe(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, with_layouts != 0, buf, cap);
+  });
 }
 
 int gpk_decode_occupancy(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, int with_layouts, int* blocks_per_cu) {
@@ -882,19 +865,15 @@ int gpk_decode_occupancy(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, in
   gpk::KParams P;
   int rc = make_params(c, p, b, nullptr, P);
   if (rc) return rc;
-  std::lock_guard<std::mutex> g(c->mu);
-  gpk::DeviceScope dscope(c->device);
-  HIPCHK(dscope.err);
-  int slot = 0;
-  rc = upload(c, p, P, &slot, c->stream);
-  if (rc) return rc;
-  if (with_layouts == GPK_NAME_FIELDS) {
-    P.fields = reinterpret_cast<gpk_fields*>(16);  // described, never written
-    HIPCHK(gpk_launch_decode_fields(&P, nullptr, blocks_per_cu));
+  return with_tables(c, p, P, c->stream, false, [&]() -> int {
+    if (with_layouts == GPK_NAME_FIELDS) {
+      P.fields = reinterpret_cast<gpk_fields*>(16);  // described, never written
+      HIPCHK(gpk_launch_decode_fields(&P, nullptr, blocks_per_cu));
+      return GPK_OK;
+    }
+    HIPCHK(gpk_launch_occupancy(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, with_layouts != 0, blocks_per_cu));
     return GPK_OK;
-  }
-  HIPCHK(gpk_launch_occupancy(&P, (p->outputs & GPK_OUT_L4_CSUM) != 0, with_layouts != 0, blocks_per_cu));
-  return GPK_OK;
+  });
 }
 
 static int ensure_dbuf(gpk_ctx* c, size_t bytes) {

@@ -40,6 +40,9 @@ namespace gpk {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
+// Tuning values, overridable with -D (make variant, tools/ab_inproc.py). The
+// code paths the A/B rounds settled are no longer knobs: DESIGN.md keeps their
+// tables and names the last commit that builds them.
 #ifndef GPK_WAVES_PER_EU
 #define GPK_WAVES_PER_EU 6  // <= 80 VGPRs: 6 waves/SIMD, matching the 6 blocks per CU the LDS allows
 #endif
@@ -49,18 +52,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifndef GPK_W4_WAVES
 #define GPK_W4_WAVES 8  // 4-chunk window kernel: 64 VGPRs
 #endif
-#ifndef GPK_MID_W5
-#define GPK_MID_W5 1  // small-packet kernels of parsers without IPv6: dword-aligned 5-chunk window
-#endif
 #ifndef GPK_MID_MAXMEAN
-#define GPK_MID_MAXMEAN 256  // ... for batches whose mean packet (batch bytes / packets) is under this
-#endif
-#ifndef GPK_MID_IP6
-#define GPK_MID_IP6 0  // ... for parsers with IPv6 too
-#endif
-#ifndef GPK_PB_GRAN
-#define GPK_PB_GRAN 1  // dense phase B: 16-byte chunks per lane per pass (A/B r03: 1 KiB passes, whole
-                       // lines per load instruction, beat 2 KiB passes of two half-coalesced loads by 20 %)
+#define GPK_MID_MAXMEAN 256  // small-packet kernels of parsers without IPv6: dword-aligned 5-chunk window for
+                             // batches whose mean packet (batch bytes / packets) is under this
 #endif
 #ifndef GPK_PB_DEPTH
 #define GPK_PB_DEPTH 8  // dense phase B: passes in flight (80-VGPR kernels; A/B r04b: 8 vs 6 -0.4 % C3, 10 no better)
@@ -75,16 +69,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifndef GPK_PB_DEPTHF
 #define GPK_PB_DEPTHF 4  // ... in its fused-fields variant
 #endif
-#ifndef GPK_PB_IDPERM
-#define GPK_PB_IDPERM 1  // dense phase B: lanes outside their target pass pull their own prefix (no LDS bank conflicts)
-#endif
-#ifndef GPK_PB_LDS_HT
-#define GPK_PB_LDS_HT 1  // segment head/tail chunks from the LDS header windows when they hold them
-#endif
-#ifndef GPK_BLOB_DMA
-#define GPK_BLOB_DMA 0  // each wave copies the table blob into LDS by LDS-DMA itself, no block barrier (A/B r15:
-                        // C4 +-0, C2 +1 %, C1 +5 %: the barrier was not what held the waves)
-#endif
 #ifndef GPK_BLOB_ROUND
 #define GPK_BLOB_ROUND 128  // dwords: the table blob's LDS share is rounded to this
 #endif
@@ -97,17 +81,9 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifndef GPK_PB_SDEPTH
 #define GPK_PB_SDEPTH 4  // sparse phase B: 1 KiB wave loads in flight
 #endif
-#ifndef GPK_DIAG_NOPARSE
-#define GPK_DIAG_NOPARSE 0  // timing only: skip DecodeLayers (fixed layout)
-#endif
-#ifndef GPK_SB
-#define GPK_SB 1  // stream-before-parse small-packet L4 kernel (decode_sb_kernel; A/B r12: C4 -3.6..-4.7 %)
-#endif
-#ifndef GPK_SB_BIG
-#define GPK_SB_BIG 0  // ... for big-packet batches too (C3: +1.2 %, not used)
-#endif
 #ifndef GPK_SB_WAVES
-#define GPK_SB_WAVES GPK_SMALL_WAVES  // ... its register budget (waves per SIMD; LDS allows 6 blocks per CU)
+#define GPK_SB_WAVES GPK_SMALL_WAVES  // stream-before-parse small-packet L4 kernel (decode_sb_kernel; A/B r12: C4
+                                      // -3.6..-4.7 %): its register budget (waves per SIMD; LDS allows 6 blocks per CU)
 #endif
 #ifndef GPK_SBF_WAVES
 #define GPK_SBF_WAVES 5  // ... its fused-fields variant (gpk_decode_batch_fields): 96 VGPRs, no scratch (A/B r15,
@@ -119,28 +95,11 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #ifndef GPK_DIAG_TIMES
 #define GPK_DIAG_TIMES 0  // diagnostic builds: per-wave phase timestamps into KParams.diag (tools/wave_times.py)
 #endif
-#ifndef GPK_FIELDS_STAGE
-#define GPK_FIELDS_STAGE 2  // fused fields: 1 = half records through LDS (64-byte runs), 2 = whole records (1 KiB runs;
-                            // A/B r15 C4 + fields: 6.62 against 7.74 ms)
-#endif
-#ifndef GPK_FIELDS_TEMPORAL
-#define GPK_FIELDS_TEMPORAL 0  // fused fields: record stores with the default policy instead of non-temporal (A/B r15:
-                               // +3 % with whole records, -9 % with half records)
-#endif
-#ifndef GPK_DIAG_FIELDS
-#define GPK_DIAG_FIELDS 0  // timing only: 1 = fused fields computed, not stored; 2 = stored, not read
-#endif
-#ifndef GPK_DIAG_NULLWIN
-#define GPK_DIAG_NULLWIN 0  // timing only: the stream-before-parse windows read the L2-resident table copy
-#endif
-#ifndef GPK_PB_NULL
-#define GPK_PB_NULL 0  // timing only: phase-B stream loads read nothing (zero-record descriptors)
-#endif
 
-constexpr int kGran = GPK_PB_GRAN;
-constexpr uint32_t kGranBytes = 16u * kGran;
-constexpr uint32_t kPassBytes = 64u * kGranBytes;
-static_assert(kGran == 1 || kGran == 2 || kGran == 4, "granule of 1, 2 or 4 chunks");
+// Dense phase B: one 16-byte chunk per lane per pass (A/B r03: 1 KiB passes,
+// whole lines per load instruction, beat 2 KiB passes of two half-coalesced
+// loads by 20 %).
+constexpr uint32_t kPassBytes = 64u * 16u;
 
 // Header-window loads keep the default (temporal) policy: the window's last
 // line is re-read by phase B (A/B r01: non-temporal window loads +11-23 %).
@@ -270,45 +229,6 @@ __device__ __forceinline__ u32x4 lds_chunk(uint32_t a) {
   return u32x4{p[0], p[1], p[2], p[3]};
 }
 
-// The parser's compact table blob (P.cg.words dwords) into LDS at byte
-// address lds_base by THIS wave alone, by LDS-DMA (global_load_lds_dword:
-// lane l's dword lands at M0 + 4 l; no registers held, completion counted by
-// vmcnt). Every wave of the block writes the same words to the same
-// addresses, so a wave needs only its own copy to have landed (s_waitcnt
-// vmcnt) and the block needs no barrier: before, the block's waves waited for
-// each other there (in the stream-before-parse kernel after their streams).
-// Writes stay inside the blob's LDS share (rounded to GPK_BLOB_ROUND dwords >=
-// 64); lanes past the blob re-read its last word.
-__device__ __forceinline__ void blob_dma(const KParams& P, uint32_t lds_base, uint32_t lane) {
-  const uint32_t words = P.cg.words, last = words - 1;
-  const uint64_t src = (uint64_t)(uintptr_t)P.ctab;
-  for (uint32_t k = 0; 64 * k < words; k++) {  // wave-uniform trip count
-    const uint32_t j = 64 * k + lane;
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(src + 4ull * (j < last ? j : last)), "s"(lds_base + 256u * k)
-                 : "memory");
-  }
-}
-
-// A granule: kGran consecutive 16-byte chunks.
-struct Gran {
-  u32x4 c[kGran];
-};
-__device__ __forceinline__ void gran_eo(const Gran& g, uint32_t& E, uint32_t& O) {
-#pragma unroll
-  for (int k = 0; k < kGran; k++) chunk_eo(g.c[k], E, O);
-}
-// The granule's bytes [0, n), n in 0..kGranBytes-1.
-__device__ __forceinline__ void gran_eo_below(const Gran& g, uint32_t n, uint32_t& E, uint32_t& O) {
-#pragma unroll
-  for (int k = 0; k < kGran; k++) {
-    const int m = (int)n - 16 * k;
-    chunk_eo_below(g.c[k], m < 0 ? 0u : (m > 16 ? 16u : (uint32_t)m), E, O);
-  }
-}
-
 // v_readlane_b32 returns int: widen through uint32_t, never through int
 // (sign extension of an address's low word above 2 GiB corrupts it).
 __device__ __forceinline__ uint32_t readlane32(uint32_t v, uint32_t lane) {
@@ -355,7 +275,7 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return readlane32(wav
 // return zeros without touching memory (hardware range check; a load that
 // crosses `bytes` returns zeros too, so `bytes` is a multiple of 16).
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const uint8_t* base, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, GPK_PB_NULL ? 0 : bytes, 0x00020000);
+  return __builtin_amdgcn_make_buffer_rsrc((void*)base, 0, bytes, 0x00020000);
 }
 // streamed (read-once) bytes: non-temporal (A/B r01: -7 % on C3)
 __device__ __forceinline__ u32x4 bload(__amdgpu_buffer_rsrc_t rs, uint32_t voff, uint32_t soff) {
@@ -376,12 +296,9 @@ struct WinT {
 // (25 dwords fit 5: tools/probes/occ_probe.hip; A/B r12 C4 -0.7..-3.6 %, C3
 // -1 %, profiles/r12_ab_slot24.txt). The 4-chunk kernel fits 8 blocks either way
 // and keeps the pad (C2 +4-7 % without it).
-#ifndef GPK_SLOT_PAD6
-#define GPK_SLOT_PAD6 0
-#endif
 template <int W, int AL>
 constexpr int slot_dw_of() {
-  return W * 4 + (AL == 4 ? 1 : (W >= 6 ? GPK_SLOT_PAD6 : 1));
+  return W >= 6 && AL != 4 ? W * 4 : W * 4 + 1;
 }
 
 struct Idx {
@@ -531,8 +448,8 @@ __device__ __forceinline__ int derive_key(const KParams& P, const Rd& r, const P
 // the head granule's bytes before s and the tail granule's bytes before e
 // (from the LDS header windows, else loaded), then turned into the word sum
 // of the segment's own alignment (l_to_words).
-// One pass of the dense stream into a granule slot: kGran raw-buffer loads
-// (16 bytes per lane each, consecutive lanes -> consecutive granules)
+// One pass of the dense stream into a granule slot: one raw-buffer load
+// (16 bytes per lane, consecutive lanes -> consecutive granules; non-temporal)
 // written in place ("+v": the slot keeps its registers across the loop, so
 // the stream needs no register rotation and no drain at the loop edge).
 // Issued as inline asm, which the compiler's wait-count pass does not see:
@@ -540,45 +457,18 @@ __device__ __forceinline__ int derive_key(const KParams& P, const Rd& r, const P
 // allocator believes the asm wrote the slot at once and could copy or spill
 // it while the load is in flight; every build's device code is therefore
 // checked for that (tools/check_stream_isa.py, run by the Makefile).
-#ifndef GPK_STREAM_NT
-#define GPK_STREAM_NT 1  // phase-B stream loads non-temporal
-#endif
-#if GPK_STREAM_NT
-#define GPK_SPOL " nt"
-#else
-#define GPK_SPOL ""
-#endif
-__device__ __forceinline__ void slot_load(u32x4 (&c)[kGran], __amdgpu_buffer_rsrc_t rs, uint32_t vo,
-                                          uint32_t soff) {
-  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" GPK_SPOL : "+v"(c[0]) : "v"(vo), "s"(rs), "s"(soff) : "memory");
-  if (kGran > 1)
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:16" GPK_SPOL
-                 : "+v"(c[kGran > 1 ? 1 : 0]) : "v"(vo), "s"(rs), "s"(soff) : "memory");
-  if (kGran > 2) {
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:32" GPK_SPOL
-                 : "+v"(c[kGran > 2 ? 2 : 0]) : "v"(vo), "s"(rs), "s"(soff) : "memory");
-    asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:48" GPK_SPOL
-                 : "+v"(c[kGran > 3 ? 3 : 0]) : "v"(vo), "s"(rs), "s"(soff) : "memory");
-  }
+__device__ __forceinline__ void slot_load(u32x4& c, __amdgpu_buffer_rsrc_t rs, uint32_t vo, uint32_t soff) {
+  asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen nt" : "+v"(c) : "v"(vo), "s"(rs), "s"(soff) : "memory");
 }
 // All but the youngest N vector-memory loads of this wave have completed.
 // The slot's registers are operands, so no use of them moves above the wait.
 template <int N>
-__device__ __forceinline__ void slot_wait(u32x4 (&c)[kGran]) {
-  if (kGran == 1)
-    asm volatile("s_waitcnt vmcnt(%1)" : "+v"(c[0]) : "n"(N) : "memory");
-  else if (kGran == 2)
-    asm volatile("s_waitcnt vmcnt(%2)" : "+v"(c[0]), "+v"(c[kGran > 1 ? 1 : 0]) : "n"(N) : "memory");
-  else
-    asm volatile("s_waitcnt vmcnt(%4)"
-                 : "+v"(c[0]), "+v"(c[kGran > 1 ? 1 : 0]), "+v"(c[kGran > 2 ? 2 : 0]), "+v"(c[kGran > 3 ? 3 : 0])
-                 : "n"(N)
-                 : "memory");
+__device__ __forceinline__ void slot_wait(u32x4& c) {
+  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(c) : "n"(N) : "memory");
 }
 
 // slot_wait with a count known after unrolling (the tail's per-slot counts)
-__device__ __forceinline__ void slot_wait_n(u32x4 (&c)[kGran], int n) {
-  static_assert(kGran == 1, "counts in loads");
+__device__ __forceinline__ void slot_wait_n(u32x4& c, int n) {
   switch (n) {
     case 0: slot_wait<0>(c); break;
     case 1: slot_wait<1>(c); break;
@@ -601,7 +491,7 @@ __device__ __forceinline__ void slot_wait_n(u32x4 (&c)[kGran], int n) {
 // packed, so the first D KiB arrive while the headers are parsed.
 template <int D>
 struct Stream {
-  Gran ring[D];
+  u32x4 ring[D];
   uint64_t R0;
   uint32_t R;
   bool on;
@@ -619,9 +509,8 @@ __device__ __forceinline__ void stream_issue(const KParams& P, Stream<D>& S, uin
 #pragma unroll
   for (int d = 0; d < D; d++) {
     if (d < d0 || d >= d1) continue;
-#pragma unroll
-    for (int k = 0; k < kGran; k++) S.ring[d].c[k] = u32x4{0, 0, 0, 0};
-    slot_load(S.ring[d].c, rs, lane * kGranBytes, d * kPassBytes);
+    S.ring[d] = u32x4{0, 0, 0, 0};
+    slot_load(S.ring[d], rs, lane * 16, d * kPassBytes);
   }
 }
 
@@ -671,7 +560,7 @@ __device__ __forceinline__ void stream_start(const KParams& P, Stream<D>& S, boo
 template <int D>
 __device__ __forceinline__ void stream_drain(Stream<D>& S) {
 #pragma unroll
-  for (int d = 0; d < D; d++) slot_wait<0>(S.ring[d].c);
+  for (int d = 0; d < D; d++) slot_wait<0>(S.ring[d]);
 }
 
 // tafter: tlds holds the bytes of the granule of e from e on (the next
@@ -684,7 +573,6 @@ __device__ __forceinline__ void stream_drain(Stream<D>& S) {
 // correction L; ta: the granule of e is streamed and P(ge) is taken.
 __device__ __forceinline__ uint32_t dense_head_tail(const KParams& P, uint64_t R0, uint32_t R, bool job, uint64_t s,
                                                     uint64_t e, uint32_t hlds, uint32_t tlds, bool tafter, bool& ta) {
-  static_assert(kGran == 1, "head/tail chunks from the LDS window need 16-byte granules");
   const __amdgpu_buffer_rsrc_t rs = rsrc(P.data + R0, (R + 15) & ~15u);
   const uint32_t rsl = job ? (uint32_t)(s - R0) : 0u, rel = job ? (uint32_t)(e - R0) : 0u;
   ta = tafter && rel < R;  // the granule of e is streamed: P(ge) exists
@@ -702,21 +590,23 @@ __device__ __forceinline__ uint32_t dense_segment_sums(const KParams& P, Stream<
   const __amdgpu_buffer_rsrc_t rs = rsrc(P.data + R0, (R + 15) & ~15u);
   const uint32_t rsl = job ? (uint32_t)(s - R0) : 0u, rel = job ? (uint32_t)(e - R0) : 0u;
   const uint32_t np = (R + kPassBytes - 1) / kPassBytes;  // wave-uniform
-  const uint32_t vo = lane * kGranBytes;
-  Gran (&ring)[D] = S.ring;
-  const int32_t a = (int32_t)(rsl / kGranBytes) - 1, b = (int32_t)(rel / kGranBytes) - (ta ? 0 : 1);
+  const uint32_t vo = lane * 16;
+  u32x4 (&ring)[D] = S.ring;
+  const int32_t a = (int32_t)(rsl / 16) - 1, b = (int32_t)(rel / 16) - (ta ? 0 : 1);
   const int32_t pa = a >> 6, pb = b >> 6;  // -1 never matches
   const int32_t la = (a & 63) << 2, lb = (b & 63) << 2, ll = (int32_t)lane << 2;
   uint32_t xa = 0, xb = 0, c = 0;
   // One pass: slot d holds pass p; refill it with pass p + D when asked.
+  // Lanes outside their target pass pull their own prefix (no LDS bank
+  // conflicts).
   auto pass = [&](const int d, const int32_t p, const bool refill) __attribute__((always_inline)) {
-    const uint32_t g = chunk_l(ring[d].c[0], 0u);
-    if (refill) slot_load(ring[d].c, rs, vo, (uint32_t)(p + D) * kPassBytes);
+    const uint32_t g = chunk_l(ring[d], 0u);
+    if (refill) slot_load(ring[d], rs, vo, (uint32_t)(p + D) * kPassBytes);
     const uint32_t sc = wave_scan(g);
     const uint32_t Pf = sc + c;
     const bool ma = pa == p, mb = pb == p;
-    const uint32_t ya = (uint32_t)__builtin_amdgcn_ds_bpermute(GPK_PB_IDPERM ? (ma ? la : ll) : la, (int)Pf);
-    const uint32_t yb = (uint32_t)__builtin_amdgcn_ds_bpermute(GPK_PB_IDPERM ? (mb ? lb : ll) : lb, (int)Pf);
+    const uint32_t ya = (uint32_t)__builtin_amdgcn_ds_bpermute(ma ? la : ll, (int)Pf);
+    const uint32_t yb = (uint32_t)__builtin_amdgcn_ds_bpermute(mb ? lb : ll, (int)Pf);
     xa = ma ? ya : xa;
     xb = mb ? yb : xb;
     c += readlane32(sc, 63);
@@ -727,7 +617,7 @@ __device__ __forceinline__ uint32_t dense_segment_sums(const KParams& P, Stream<
   for (; p0 + D <= np; p0 += D) {
 #pragma unroll
     for (int d = 0; d < D; d++) {
-      slot_wait<(D - 1) * kGran>(ring[d].c);  // slot d's loads are the oldest in flight
+      slot_wait<D - 1>(ring[d]);  // slot d's loads are the oldest in flight
       pass(d, (int32_t)(p0 + d), true);
     }
   }
@@ -736,7 +626,7 @@ __device__ __forceinline__ uint32_t dense_segment_sums(const KParams& P, Stream<
 #pragma unroll
   for (int d = 0; d < D - 1; d++) {
     if (p0 + d >= np) break;
-    slot_wait_n(ring[d].c, D - 1 - d);
+    slot_wait_n(ring[d], D - 1 - d);
     pass(d, (int32_t)(p0 + d), false);
   }
   L += xb - xa;
@@ -876,18 +766,17 @@ struct SbPkt {
 template <int D>
 __device__ __forceinline__ uint32_t sb_stream(const KParams& P, Stream<D>& S, uint64_t R0, uint32_t R, uint32_t lane,
                                               int32_t a1, int32_t b) {
-  static_assert(kGran == 1, "one 16-byte granule per lane per pass");
   stream_issue(P, S, R0, R, lane, 0, D);
   const __amdgpu_buffer_rsrc_t rs = rsrc(P.data + R0, (R + 15) & ~15u);
   const uint32_t np = (R + kPassBytes - 1) / kPassBytes;  // wave-uniform
-  const uint32_t vo = lane * kGranBytes;
-  Gran (&ring)[D] = S.ring;
+  const uint32_t vo = lane * 16;
+  u32x4 (&ring)[D] = S.ring;
   const int32_t pa = a1 >> 6, pb = b >> 6;  // -1 never matches
   const int32_t la = (a1 & 63) << 2, lb = (b & 63) << 2, ll = (int32_t)lane << 2;
   uint32_t xa = 0, xb = 0, c = 0;
   auto pass = [&](const int d, const int32_t p, const bool refill) __attribute__((always_inline)) {
-    const uint32_t gl = chunk_l(ring[d].c[0], 0u);
-    if (refill) slot_load(ring[d].c, rs, vo, (uint32_t)(p + D) * kPassBytes);
+    const uint32_t gl = chunk_l(ring[d], 0u);
+    if (refill) slot_load(ring[d], rs, vo, (uint32_t)(p + D) * kPassBytes);
     const uint32_t sc = wave_scan(gl);
     const uint32_t Pf = sc + c;
     const bool ma = pa == p, mb = pb == p;
@@ -905,7 +794,7 @@ __device__ __forceinline__ uint32_t sb_stream(const KParams& P, Stream<D>& S, ui
   do {
 #pragma unroll
     for (int d = 0; d < D; d++) {
-      slot_wait<(D - 1) * kGran>(ring[d].c);
+      slot_wait<D - 1>(ring[d]);
       pass(d, (int32_t)(p0 + d), true);
     }
     p0 += D;
@@ -913,7 +802,7 @@ __device__ __forceinline__ uint32_t sb_stream(const KParams& P, Stream<D>& S, ui
 #pragma unroll
   for (int d = 0; d < D - 1; d++) {
     if (p0 + d >= np) break;
-    slot_wait_n(ring[d].c, D - 1 - d);
+    slot_wait_n(ring[d], D - 1 - d);
     pass(d, (int32_t)(p0 + d), false);
   }
   stream_drain(S);
@@ -944,20 +833,17 @@ struct RdF {
   }
 };
 
-// The wave's 64 records of 128 bytes out as coalesced stores, staged through
-// the wave's LDS window slots (>= 4 KiB) in two halves: lane l puts the 64
-// bytes of its record's half into LDS (16-byte chunk c at chunk position
-// c ^ (l & 3), spreading the banks), then store k of the half writes records
-// 16k .. 16k+15, lane l carrying chunk l & 3 of record 16k + l / 4 (16 runs of
-// 64 contiguous bytes per instruction; the halves meet in L2). Runs with the
+// The wave's 64 records of 128 bytes out as coalesced non-temporal stores,
+// staged whole through the wave's LDS window slots (6 KiB): lanes
+// [48g, 48g + 48) put their records into LDS (16-byte chunk c at chunk
+// position c ^ (l & 7), spreading the banks), then each store writes 8 whole
+// records, 1 KiB contiguous (A/B r15 C4 + fields: 6.62 ms against 7.74 ms with
+// half records in 64-byte runs; default-policy stores +3 %). Runs with the
 // whole wave active, after every lane's last window read (LDS operations of a
 // wave complete in order; the compiler barriers keep them in program order).
 __device__ __forceinline__ void fields_store(const KParams& P, const uint32_t (&w)[32], uint32_t wave_dw, uint32_t lane,
                                              uint64_t first) {
   u32x4* out = reinterpret_cast<u32x4*>(P.fields + first);
-#if GPK_FIELDS_STAGE == 2
-  // whole records: lanes [48g, 48g + 48) put theirs into the 6 KiB (chunk c at
-  // c ^ (l & 7)), then 1 KiB stores of 8 whole records each
 #pragma unroll
   for (uint32_t g = 0; g < 2; g++) {
     const uint32_t l0 = 48 * g, nrec = g ? 16u : 48u;
@@ -975,35 +861,7 @@ __device__ __forceinline__ void fields_store(const KParams& P, const uint32_t (&
       if (g && k >= 2) break;
       const uint32_t q = 8 * k + (lane >> 3), c = lane & 7, rr = l0 + q;
       const u32x4 v = *reinterpret_cast<const u32x4*>(gpk_smem + wave_dw + q * 32 + 4 * (c ^ (q & 7)));
-      if (first + rr < P.n) {
-        if (GPK_FIELDS_TEMPORAL)
-          out[8 * rr + c] = v;
-        else
-          __builtin_nontemporal_store(v, out + 8 * rr + c);
-      }
-    }
-  }
-  asm volatile("" ::: "memory");
-  return;
-#endif
-#pragma unroll
-  for (int h = 0; h < 2; h++) {
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (uint32_t c = 0; c < 4; c++)
-      *reinterpret_cast<u32x4*>(gpk_smem + wave_dw + lane * 16 + 4 * (c ^ (lane & 3))) =
-          u32x4{w[16 * h + 4 * c], w[16 * h + 4 * c + 1], w[16 * h + 4 * c + 2], w[16 * h + 4 * c + 3]};
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (uint32_t k = 0; k < 4; k++) {
-      const uint32_t rr = 16 * k + (lane >> 2), c = lane & 3;
-      const u32x4 v = *reinterpret_cast<const u32x4*>(gpk_smem + wave_dw + rr * 16 + 4 * (c ^ (rr & 3)));
-      if (first + rr < P.n) {
-        if (GPK_FIELDS_TEMPORAL)
-          out[8 * rr + 4 * h + c] = v;
-        else
-          __builtin_nontemporal_store(v, out + 8 * rr + 4 * h + c);
-      }
+      if (first + rr < P.n) __builtin_nontemporal_store(v, out + 8 * rr + c);
     }
   }
   asm volatile("" ::: "memory");
@@ -1033,25 +891,8 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
   q.init();
   Outcome s{0, 0, 0, 0};
   bool done = false;
-#if GPK_DIAG_NOPARSE  // timing only: a fixed Eth/IPv4/UDP|TCP layout, no decoding
-  if (active) {
-    q.s_eth = 0;
-    q.e_eth = cl;
-    q.s_ip4 = 14;
-    q.e_ip4 = cl;
-    q.last_net = GPK_DEC_IPV4;
-    q.transport = lds8(r.lb + 23) == 6 ? GPK_DEC_TCP : GPK_DEC_UDP;
-    q.s_tcp = q.s_udp = 34;
-    q.e_tcp = q.e_udp = cl;
-    q.udp_hlen = cl - 34;
-    q.layers = 0x931;
-    q.nlayers = 3;
-  }
-  (void)done;
-#else
   if (active && P.fast) done = fast_parser(P, T, r, cl, q, s);
   if (active && !done) s = run_parser<false>(P, T, r, cl, q);
-#endif
 
   // fused fields: the decoders' last slices in compact form (presence, the
   // starts the fields read, the IPv4 end), live to the fields epilogue instead
@@ -1178,20 +1019,8 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
   // never hold registers at the same time.
   auto emit_fields = [&]() __attribute__((always_inline)) {
     uint32_t fw[32];
-#if GPK_DIAG_FIELDS == 2  // timing only: the stores without the field reads
-#pragma unroll
-    for (int k = 0; k < 32; k++) fw[k] = fst[k & 7] + fpres * k;
-#else
     gpkf::fields_words(RdF{r}, fpres, fst, fip4e, fw);
-#endif
-#if GPK_DIAG_FIELDS == 1  // timing only: the field reads without the record stores
-    uint32_t x = 0;
-#pragma unroll
-    for (int k = 0; k < 32; k++) x ^= fw[k];
-    if (x == 0x9E3779B9u) P.fields[i].present = x;
-#else
     fields_store(P, fw, slot_dw - lane * kSlotStride, lane, i - lane);
-#endif
   };
 
   // ---- Phase B: segment sums ---------------------------------------------
@@ -1255,10 +1084,10 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
     uint32_t hlds = ~0u, tlds = ~0u;
     bool tafter = false;
     if (AL == 16) {
-      if (GPK_PB_LDS_HT && job && (js >> 4) - c0 < nch) hlds = slot_dw * 4 + 16 * (uint32_t)((js >> 4) - c0);
-      if (GPK_PB_LDS_HT && job && (je >> 4) - c0 < nch)
+      if (job && (js >> 4) - c0 < nch) hlds = slot_dw * 4 + 16 * (uint32_t)((js >> 4) - c0);
+      if (job && (je >> 4) - c0 < nch)
         tlds = slot_dw * 4 + 16 * (uint32_t)((je >> 4) - c0);
-      else if (GPK_PB_LDS_HT && job && lane < 63 && nnch && (noff >> 4) == (je >> 4))
+      else if (job && lane < 63 && nnch && (noff >> 4) == (je >> 4))
         tlds = (slot_dw + kSlotStride) * 4;
     } else {
       // the window holds batch bytes [wb, wb + m + win): a head/tail chunk
@@ -1267,11 +1096,11 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
       const uint64_t wb = g.wb;
       const uint32_t vb = m + win;
       const uint32_t hb = (uint32_t)((js & ~15ull) - wb), tb = (uint32_t)((je & ~15ull) - wb);
-      if (GPK_PB_LDS_HT && job && hb < vb && hb + (uint32_t)(js & 15) <= vb) hlds = slot_dw * 4 + hb;
+      if (job && hb < vb && hb + (uint32_t)(js & 15) <= vb) hlds = slot_dw * 4 + hb;
       const uint32_t nm = (uint32_t)__shfl_down((int)m, 1);
-      if (GPK_PB_LDS_HT && job && tb < vb && tb + (uint32_t)(je & 15) <= vb) {
+      if (job && tb < vb && tb + (uint32_t)(je & 15) <= vb) {
         tlds = slot_dw * 4 + tb;
-      } else if (GPK_PB_LDS_HT && job && lane < 63 && nnch && noff == je) {
+      } else if (job && lane < 63 && nnch && noff == je) {
         // the next packet starts at e: its window (packet byte 0 at slot byte
         // nm) holds the granule's bytes from e on, at a dword-aligned address
         tlds = (slot_dw + kSlotStride) * 4 + nm - (uint32_t)(je & 15);
@@ -1343,6 +1172,22 @@ __device__ __forceinline__ void decode_packet(const KParams& P, const TT& T, uin
   }
 }
 
+#if GPK_DIAG_TIMES
+// A kernel's last step in diagnostic builds: the wave's dt[0..7] out through
+// lanes 0-7. Timestamps (100 MHz realtime counter, one clock for all XCDs),
+// dt[6] = HW_ID | XCC_ID << 32, dt[7] = the phase-B region bytes | job lanes << 32.
+__device__ __forceinline__ void diag_store(const KParams& P, uint64_t (&dt)[8], uint32_t wave, uint32_t lane) {
+  dt[5] = __builtin_amdgcn_s_memrealtime();
+  dt[6] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
+  if (P.diag && lane < 8) {
+    uint64_t v = dt[0];
+#pragma unroll
+    for (int k = 1; k < 8; k++) v = lane == (uint32_t)k ? dt[k] : v;
+    P.diag[((uint64_t)blockIdx.x * kWaves + wave) * 8 + lane] = v;
+  }
+}
+#endif
+
 // kCompact: the parser's lookup tables are copied into LDS once per block
 // (after the header-window slots) and every NextLayerType lookup is an LDS
 // read; otherwise they are read from the global DevTables. Either way the
@@ -1379,10 +1224,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W == 4 ?
   const WinGeo g0 = win_geo<W, AL>(P, c0, i0 < P.n);
   WinT<W> w0;
   load_window<W, AL>(P, g0, w0);
-  if (kCompact && GPK_BLOB_DMA) {
-    static_assert(GPK_BLOB_ROUND % 64 == 0, "the blob's LDS share holds whole 64-dword DMA rows");
-    blob_dma(P, (uint32_t)(uintptr_t)gpk_smem + 4u * base, tid & 63);
-  } else if (kCompact) {  // the table blob (<= kCtDwords): clamped indices, duplicate writes of equal values
+  if (kCompact) {  // the table blob (<= kCtDwords): clamped indices, duplicate writes of equal values
     static_assert(kCtDwords <= 3 * kBlock, "three blob words per thread");
     const uint32_t last = P.cg.words - 1;
 #pragma unroll
@@ -1393,9 +1235,6 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W == 4 ?
     __syncthreads();
   }
   store_window<W, AL>(slot_dw, w0);
-  // this wave's blob DMA has landed before the parse reads the tables (and
-  // before decode_packet issues any stream load)
-  if (kCompact && GPK_BLOB_DMA) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #if GPK_DIAG_TIMES
   dt[2] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1406,20 +1245,11 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W == 4 ?
     decode_packet<kL4, kLayout, GTab, kKeys, W, O, AL>(P, GTab{P.tab}, i0, i0 < P.n, c0.off, c0.cl, g0, slot_dw,
                                                        tid & 63, dt);
 #if GPK_DIAG_TIMES
-  // timestamps (100 MHz realtime counter, one clock for all XCDs), HW_ID | XCC_ID << 32, the
-  // phase-B region bytes | job lanes << 32
-  dt[5] = __builtin_amdgcn_s_memrealtime();
-  dt[6] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
-  if (P.diag && (tid & 63) < 8) {
-    uint64_t v = dt[0];
-#pragma unroll
-    for (int k = 1; k < 8; k++) v = (tid & 7) == (uint32_t)k ? dt[k] : v;
-    P.diag[((uint64_t)blockIdx.x * kWaves + tid / 64) * 8 + (tid & 7)] = v;
-  }
+  diag_store(P, dt, tid / 64, tid & 63);
 #endif
 }
 
-// Stream-before-parse L4 kernel (GPK_SB): the header windows go into LDS by
+// Stream-before-parse L4 kernel: the header windows go into LDS by
 // LDS-DMA (no registers held) and phase B's stream over the wave's packets is
 // issued right behind them, before DecodeLayers: the window's latency hides
 // under the stream, the stream re-reads the window lines while they are still
@@ -1445,11 +1275,7 @@ __device__ __forceinline__ void dma16(uint64_t src, uint32_t lds) {
 // packet with none reads the parser's table copy (as load_window).
 template <int W>
 __device__ __forceinline__ void window_dma(const KParams& P, const WinGeo& g, uint32_t region, uint32_t lane) {
-#if GPK_DIAG_NULLWIN  // timing only: every window from the L2-resident table copy
-  const uint64_t src = (uint64_t)(uintptr_t)P.tab;
-#else
   const uint64_t src = g.nch ? (uint64_t)(uintptr_t)(P.data + g.wb) : (uint64_t)(uintptr_t)P.tab;
-#endif
   const uint32_t last = g.nch ? g.nch - 1 : 0u;
 #pragma unroll
   for (int k = 0; k < W; k++) {
@@ -1464,9 +1290,8 @@ __device__ __forceinline__ void window_dma(const KParams& P, const WinGeo& g, ui
 
 template <bool kCompact, int O, int W = 6, bool kFields = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(O, 8))) void decode_sb_kernel(KParams P) {
-  // fields_store stages 48 whole 128-byte records (GPK_FIELDS_STAGE 2: 1536 dwords) or a half record per lane
-  // (1: 1024 dwords) in the wave's window slots, 4 W dwords per lane
-  static_assert(!kFields || 64 * 4 * W >= (GPK_FIELDS_STAGE == 2 ? 1536 : 1024),
+  // fields_store stages 48 whole 128-byte records (1536 dwords) in the wave's window slots, 4 W dwords per lane
+  static_assert(!kFields || 64 * 4 * W >= 1536,
                 "the fused fields' staging does not fit the wave's window slots");
   constexpr int D = GPK_SB_DEPTH;
   constexpr int kSbStride = 4 * W;  // one 16-byte cell per window chunk, no pad
@@ -1483,9 +1308,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(O, 8))) 
   const Idx c0 = load_index(P, i0);
   const WinGeo g0 = win_geo<W, 16>(P, c0, active);
   window_dma<W>(P, g0, (uint32_t)(uintptr_t)gpk_smem + wave * (64u * kSbStride * 4u), lane);
-  if (kCompact && GPK_BLOB_DMA) {  // this wave's own copy (the vmcnt(0) below waits for it)
-    blob_dma(P, (uint32_t)(uintptr_t)gpk_smem + 4u * base, lane);
-  } else if (kCompact) {  // the table blob (read after the barrier below)
+  if (kCompact) {  // the table blob (read after the barrier below)
     static_assert(kCtDwords <= 3 * kBlock, "three blob words per thread");
     const uint32_t last = P.cg.words - 1;
 #pragma unroll
@@ -1510,8 +1333,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(O, 8))) 
     S.on = true;
     L = sb_stream<D>(P, S, R0, R, lane, a1, b);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the windows (and this wave's blob) have landed
-  if (kCompact && !GPK_BLOB_DMA) __syncthreads();
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the windows have landed
+  if (kCompact) __syncthreads();
 #if GPK_DIAG_TIMES
   dt[2] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -1529,15 +1352,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(O, 8))) 
     decode_packet<true, false, GTab, false, W, O, 16, kSbStride, 0, true, kFields>(
         P, GTab{P.tab}, i1, i1 < P.n, c1.off, c1.cl, g1, tid1 * kSbStride, tid1 & 63, dt, SbPkt{L, R0, b, ok});
 #if GPK_DIAG_TIMES
-  dt[5] = __builtin_amdgcn_s_memrealtime();
-  dt[6] = (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 4) | (uint64_t)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32;
   dt[7] = ok ? (uint64_t)R | (uint64_t)__builtin_popcountll(__ballot(active)) << 32 : 0;
-  if (P.diag && lane < 8) {
-    uint64_t v = dt[0];
-#pragma unroll
-    for (int k = 1; k < 8; k++) v = lane == (uint32_t)k ? dt[k] : v;
-    P.diag[((uint64_t)blockIdx.x * kWaves + wave) * 8 + lane] = v;
-  }
+  diag_store(P, dt, wave, lane);
 #endif
 }
 
@@ -1603,55 +1419,99 @@ hipError_t launch_sb(const gpk::KParams* P, hipStream_t stream, int* occ) {
   return hipGetLastError();
 }
 
-// The specialisation a launch uses (gpk_launch_decode, gpk_launch_name).
+// The specialisation a launch uses: what select() decides, and what names a
+// row of kKernels (every field but `compact`, which picks the row's column).
 struct Sel {
-  bool l4, layout, compact, keys;
+  bool sb, fields;  // decode_sb_kernel, with its fused-fields epilogue
+  bool l4, layout, keys;
   int W, O, AL;
-  bool sb;
+  bool compact;
 };
 Sel select(const gpk::KParams* P, int with_l4, int with_layout) {
-  Sel s{with_l4 != 0, with_layout != 0, P->ctab != nullptr, P->key_kind != 0, gpk::kWinChunks, GPK_WAVES_PER_EU, 16,
-        false};
+  Sel s{false, false, with_l4 != 0, with_layout != 0, P->key_kind != 0, gpk::kWinChunks, GPK_WAVES_PER_EU, 16,
+        P->ctab != nullptr};
   if (s.keys) {  // fused grouping keys: no layouts (gpk_decode_group_batch)
     s.layout = false;
   } else if (!s.l4 && !s.layout && P->small_headers) {
     s.W = 4;
   } else if (!s.layout && !P->big_packets) {
     s.O = GPK_SMALL_WAVES;
-    // a dword-aligned 5-chunk window (7 blocks per CU) for the smallest packets; from a mean of
-    // GPK_MID_MAXMEAN bytes on, the stream-before-parse kernel (A/B r15: C1, mean 113 B, +2.7 % with
-    // it; C4's packets through a parser without IPv6, mean 362 B, -8 %)
-    if (GPK_MID_W5 && (P->mid_headers || GPK_MID_IP6) && P->data_end && P->mean_bytes < GPK_MID_MAXMEAN) {
+    // a dword-aligned 5-chunk window (7 blocks per CU) for the smallest packets of parsers without IPv6; from
+    // a mean of GPK_MID_MAXMEAN bytes on, the stream-before-parse kernel (A/B r15: C1, mean 113 B, +2.7 %
+    // with it; C4's packets through a parser without IPv6, mean 362 B, -8 %)
+    if (P->mid_headers && P->data_end && P->mean_bytes < GPK_MID_MAXMEAN) {
       s.W = 5;
       s.AL = 4;
     }
   }
-  s.sb = GPK_SB && s.l4 && !s.layout && !s.keys && s.W == gpk::kWinChunks && s.AL == 16 &&
-         (GPK_SB_BIG || s.O != GPK_WAVES_PER_EU);
+  // the L4 checksum of small-packet batches in a 6-chunk window: stream before the parse (A/B r12: C4
+  // -3.6..-4.7 %; big-packet batches C3 +1.2 %, so not there)
+  s.sb = s.l4 && !s.layout && !s.keys && s.W == gpk::kWinChunks && s.AL == 16 && s.O != GPK_WAVES_PER_EU;
+  if (s.sb) s.O = GPK_SB_WAVES;
   return s;
 }
+// The fused decode + layer fields launch (gpk_decode_batch_fields without
+// layouts): the stream-before-parse kernel with its fields epilogue, for every
+// parser and batch (its 6-chunk window holds every header the fast path reads;
+// the rest comes from memory).
+Sel select_fields(const gpk::KParams* P) {
+  return Sel{true, true, true, false, false, gpk::kWinChunks, GPK_SBF_WAVES, 16, P->ctab != nullptr};
+}
 
-template <bool kCompact>
-hipError_t launch_sel(const gpk::KParams* P, const Sel& s, hipStream_t stream, int* occ) {
-  constexpr int W = gpk::kWinChunks;
-  if (s.sb) {
-#if GPK_SB_BIG
-    if (s.O == GPK_WAVES_PER_EU) return launch_sb<kCompact, GPK_WAVES_PER_EU>(P, stream, occ);
-#endif
-    return launch_sb<kCompact, GPK_SB_WAVES>(P, stream, occ);
+// Every instantiated specialisation, once: its template arguments and its
+// launcher for global ([0]) and compact ([1]) tables. Launch, occupancy and
+// name all come from the row select()'s answer finds; an answer without a row
+// is an error, never another kernel.
+struct Row {
+  Sel id;
+  hipError_t (*fn[2])(const gpk::KParams*, hipStream_t, int*);
+};
+template <bool kL4, bool kLayout, bool kKeys = false, int W = gpk::kWinChunks, int O = GPK_WAVES_PER_EU, int AL = 16>
+constexpr Row row() {
+  return Row{{false, false, kL4, kLayout, kKeys, W, O, AL, false},
+             {launch<kL4, kLayout, false, kKeys, W, O, AL>, launch<kL4, kLayout, true, kKeys, W, O, AL>}};
+}
+template <int O, bool kFields>
+constexpr Row row_sb() {
+  return Row{{true, kFields, true, false, false, gpk::kWinChunks, O, 16, false},
+             {launch_sb<false, O, gpk::kWinChunks, kFields>, launch_sb<true, O, gpk::kWinChunks, kFields>}};
+}
+const Row kKernels[] = {
+    row<true, false>(),                                  // big packets
+    row<false, false>(),
+    row<true, true>(),                                   // with layouts
+    row<false, true>(),
+    row<true, false, true>(),                            // with fused grouping keys
+    row<false, false, true>(),
+    row<false, false, false, 4>(),                       // header-only parsers, no L4 checksum
+    row<true, false, false, 5, GPK_SMALL_WAVES, 4>(),    // small packets, no IPv6, mean under GPK_MID_MAXMEAN
+    row<false, false, false, 5, GPK_SMALL_WAVES, 4>(),
+    row<false, false, false, gpk::kWinChunks, GPK_SMALL_WAVES>(),  // other small packets without the L4 checksum
+    row_sb<GPK_SB_WAVES, false>(),                       // ... and with it
+    row_sb<GPK_SBF_WAVES, true>(),                       // fused fields
+};
+const Row* find_row(const Sel& s) {
+  for (const Row& r : kKernels) {
+    const Sel& k = r.id;
+    if (k.sb == s.sb && k.fields == s.fields && k.l4 == s.l4 && k.layout == s.layout && k.keys == s.keys && k.W == s.W &&
+        k.O == s.O && k.AL == s.AL)
+      return &r;
   }
-  if (s.keys)
-    return s.l4 ? launch<true, false, kCompact, true>(P, stream, occ) : launch<false, false, kCompact, true>(P, stream, occ);
-  if (s.W == 4) return launch<false, false, kCompact, false, 4>(P, stream, occ);
-  if (s.l4 && s.layout) return launch<true, true, kCompact>(P, stream, occ);
-  if (s.l4)
-    return s.O == GPK_WAVES_PER_EU ? launch<true, false, kCompact>(P, stream, occ)
-           : s.AL == 4             ? launch<true, false, kCompact, false, 5, GPK_SMALL_WAVES, 4>(P, stream, occ)
-                                   : launch<true, false, kCompact, false, W, GPK_SMALL_WAVES>(P, stream, occ);
-  if (s.layout) return launch<false, true, kCompact>(P, stream, occ);
-  return s.O == GPK_WAVES_PER_EU ? launch<false, false, kCompact>(P, stream, occ)
-         : s.AL == 4             ? launch<false, false, kCompact, false, 5, GPK_SMALL_WAVES, 4>(P, stream, occ)
-                                 : launch<false, false, kCompact, false, W, GPK_SMALL_WAVES>(P, stream, occ);
+  return nullptr;
+}
+hipError_t launch_row(const gpk::KParams* P, const Sel& s, hipStream_t stream, int* occ) {
+  const Row* r = find_row(s);
+  return r ? r->fn[s.compact](P, stream, occ) : hipErrorInvalidValue;
+}
+// The kernel's name as the profiler prints it; negative when there is no such kernel.
+int describe_row(const Sel& s, char* buf, size_t cap) {
+  const Row* r = find_row(s);
+  if (!r) return -1;
+  auto tf = [](bool b) { return b ? "true" : "false"; };
+  const Sel& k = r->id;
+  if (k.sb) return snprintf(buf, cap, "gpk::decode_sb_kernel<%s,%d,%d,%s>", tf(s.compact), k.O, k.W, tf(k.fields));
+  return snprintf(buf, cap, "gpk::decode_kernel<%s,%s,%s,%s,%d,%d,%d>", tf(k.l4), tf(k.layout), tf(s.compact), tf(k.keys),
+                  k.W, k.O, k.AL);
 }
 
 }  // namespace
@@ -1659,41 +1519,27 @@ hipError_t launch_sel(const gpk::KParams* P, const Sel& s, hipStream_t stream, i
 extern "C" hipError_t gpk_launch_decode(const gpk::KParams* P, int with_l4, int with_layout, hipStream_t stream) {
   if (P->n == 0) return hipSuccess;
   if (P->key_kind && with_layout) return hipErrorInvalidValue;
-  const Sel s = select(P, with_l4, with_layout);
-  return s.compact ? launch_sel<true>(P, s, stream, nullptr) : launch_sel<false>(P, s, stream, nullptr);
+  return launch_row(P, select(P, with_l4, with_layout), stream, nullptr);
 }
 
 // Blocks of that specialisation resident per CU (registers and this launch's LDS).
 extern "C" hipError_t gpk_launch_occupancy(const gpk::KParams* P, int with_l4, int with_layout, int* blocks) {
-  const Sel s = select(P, with_l4, with_layout);
-  return s.compact ? launch_sel<true>(P, s, nullptr, blocks) : launch_sel<false>(P, s, nullptr, blocks);
+  return launch_row(P, select(P, with_l4, with_layout), nullptr, blocks);
 }
 
 // Name of the kernel specialisation gpk_launch_decode would launch.
 extern "C" int gpk_launch_describe(const gpk::KParams* P, int with_l4, int with_layout, char* buf, size_t cap) {
-  const Sel s = select(P, with_l4, with_layout);
-  if (s.sb)
-    return snprintf(buf, cap, "gpk::decode_sb_kernel<%s,%d,%d,false>", s.compact ? "true" : "false",
-                    s.O == GPK_WAVES_PER_EU ? s.O : GPK_SB_WAVES, gpk::kWinChunks);
-  return snprintf(buf, cap, "gpk::decode_kernel<%s,%s,%s,%s,%d,%d,%d>", s.l4 ? "true" : "false",
-                  s.layout ? "true" : "false", s.compact ? "true" : "false", s.keys ? "true" : "false", s.W,
-                  s.W == 4 ? 6 : s.O, s.AL);
+  return describe_row(select(P, with_l4, with_layout), buf, cap);
 }
 
-// The fused decode + layer fields launch (gpk_decode_batch_fields without
-// layouts): the stream-before-parse kernel with its fields epilogue, for every
-// parser and batch (its 6-chunk window holds every header the fast path reads;
-// the rest comes from memory). occ: report resident blocks instead; name:
-// describe it instead.
+// The fused-fields launch (select_fields). occ: report resident blocks instead.
 extern "C" hipError_t gpk_launch_decode_fields(const gpk::KParams* P, hipStream_t stream, int* occ) {
   if (!occ && P->n == 0) return hipSuccess;
   if (P->key_kind || !P->fields) return hipErrorInvalidValue;
-  return P->ctab ? launch_sb<true, GPK_SBF_WAVES, gpk::kWinChunks, true>(P, stream, occ)
-                 : launch_sb<false, GPK_SBF_WAVES, gpk::kWinChunks, true>(P, stream, occ);
+  return launch_row(P, select_fields(P), stream, occ);
 }
 extern "C" int gpk_launch_describe_fields(const gpk::KParams* P, char* buf, size_t cap) {
-  return snprintf(buf, cap, "gpk::decode_sb_kernel<%s,%d,%d,true>", P->ctab ? "true" : "false", GPK_SBF_WAVES,
-                  gpk::kWinChunks);
+  return describe_row(select_fields(P), buf, cap);
 }
 
 extern "C" hipError_t gpk_launch_list(const gpk::KParams* P, uint64_t index, int64_t* out, uint32_t cap,

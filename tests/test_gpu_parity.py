@@ -401,3 +401,101 @@ def test_phase_b_layouts(gpu_ctx, layout, layouts):
         dev = gpu_ctx.decode_host(dp, data, off, cap, layouts=layouts)
         ref = oracle_parser(cfg).decode(data, off, cap, nthreads=8, layouts=layouts)
         assert_same(dev, ref, "%s/%s/layouts=%s" % (layout, name, layouts))
+
+
+# ---- kernel selection, pinned -------------------------------------------------
+# The 12 specialisations select() can answer with (gpk_kernels.hip kKernels), as
+# gpk_decode_kernel_name prints them; %s is the table mode ("true": compact LDS
+# tables, "false": GPK_TABLES_GLOBAL).
+K_BIG = "gpk::decode_kernel<true,false,%s,false,6,6,16>"
+K_BIG_NOL4 = "gpk::decode_kernel<false,false,%s,false,6,6,16>"
+K_LAY = "gpk::decode_kernel<true,true,%s,false,6,6,16>"
+K_LAY_NOL4 = "gpk::decode_kernel<false,true,%s,false,6,6,16>"
+K_W4 = "gpk::decode_kernel<false,false,%s,false,4,6,16>"
+K_W5 = "gpk::decode_kernel<true,false,%s,false,5,7,4>"
+K_W5_NOL4 = "gpk::decode_kernel<false,false,%s,false,5,7,4>"
+K_SMALL_NOL4 = "gpk::decode_kernel<false,false,%s,false,6,7,16>"
+K_SB = "gpk::decode_sb_kernel<%s,7,6,false>"
+K_FIELDS = "gpk::decode_sb_kernel<%s,5,6,true>"
+# (with fused grouping keys: decode_kernel<l4,false,%s,true,6,6,16>, which the C
+# ABI has no name query for; those launches are checked by their results)
+
+# parser -> batch (synthetic config: mean packet) -> kernel without layouts for
+# (L4 checksum on, off). With layouts every parser and batch takes K_LAY /
+# K_LAY_NOL4, the fused fields launch K_FIELDS.
+SELECTION_PARSERS = {
+    "eth_ip4_udp_payload": "header-only: no Dot1Q/IPv6/TCP decoder (4-chunk window without the L4 checksum)",
+    "eth_ip4_tcp_payload": "no IPv6 decoder (dword-aligned 5-chunk window under GPK_MID_MAXMEAN = 256 B)",
+    "statsassembly": "full parser",
+}
+SELECTION_BATCHES = {2: (0, 256), 4: (256, 1024), 3: (1024, 1 << 20)}  # synth config: its mean packet's band, bytes
+SELECTION = {
+    "eth_ip4_udp_payload": {2: (K_W5, K_W4), 4: (K_SB, K_W4), 3: (K_BIG, K_W4)},
+    "eth_ip4_tcp_payload": {2: (K_W5, K_W5_NOL4), 4: (K_SB, K_SMALL_NOL4), 3: (K_BIG, K_BIG_NOL4)},
+    "statsassembly": {2: (K_SB, K_SMALL_NOL4), 4: (K_SB, K_SMALL_NOL4), 3: (K_BIG, K_BIG_NOL4)},
+}
+SELECTION_N = 257  # two workgroups, the second with one active lane: inactive-lane prologue and a partial wave
+_selection_cache = {}
+
+
+def selection_case(name, synth_cfg, l4):
+    """The 257-packet batch of a synthetic config and the oracle's results for
+    it (with and without layouts), computed once per parser, batch and outputs."""
+    from gopacket_amd import synth
+    key = (name, synth_cfg, l4)
+    if key not in _selection_cache:
+        if ("batch", synth_cfg) not in _selection_cache:
+            _selection_cache["batch", synth_cfg] = synth.host_batch(synth_cfg, 31, SELECTION_N)
+        data, off, cap = _selection_cache["batch", synth_cfg]
+        cfg = dict(CONFIGS[name], outputs=7 if l4 else 5)  # GPK_OUT_L4_CSUM = 2
+        op = oracle_parser(cfg)
+        _selection_cache[key] = (cfg, data, off, cap, op.decode(data, off, cap, nthreads=1, layouts=True),
+                                 op.decode(data, off, cap, nthreads=1, layouts=False))
+    return _selection_cache[key]
+
+
+@pytest.mark.parametrize("tables", ["compact", "global"])
+def test_selection_is_pinned(gpu_ctx, tables):
+    """Every selection input (L4 checksum, layouts / fused fields / fused keys,
+    the parser's header class, the batch's mean packet, the table mode) takes
+    the kernel named here, that kernel is resident at least once per CU, and
+    257 packets through it give the oracle's results bit for bit."""
+    import torch
+    from gopacket_amd import _lib, flows
+    mode = "true" if tables == "compact" else "false"
+    grouper = flows.Grouper(SELECTION_N)
+    gpu_ctx.set_table_mode(_lib.TABLES_GLOBAL if tables == "global" else _lib.TABLES_AUTO)
+    try:
+        for name in SELECTION_PARSERS:
+            for synth_cfg, (lo, hi) in SELECTION_BATCHES.items():
+                for l4 in (True, False):
+                    cfg, data, off, cap, ref_lay, ref = selection_case(name, synth_cfg, l4)
+                    assert len(off) == SELECTION_N and lo <= len(data) // len(off) < hi
+                    dp = device_parser(cfg)
+                    what = "%s/synth%d/l4=%s/%s" % (name, synth_cfg, l4, tables)
+                    plain = SELECTION[name][synth_cfg][0 if l4 else 1]
+                    for layouts, want in ((False, plain), (True, K_LAY if l4 else K_LAY_NOL4),
+                                          (_lib.NAME_FIELDS, K_FIELDS)):
+                        assert gpu_ctx.kernel_name(dp, data, off, cap, layouts=layouts) == want % mode, (what, layouts)
+                        assert gpu_ctx.occupancy(dp, data, off, cap, layouts=layouts) >= 1, (what, layouts)
+                        if layouts == _lib.NAME_FIELDS:
+                            dev = gpu_ctx.decode_host(dp, data, off, cap, layouts=False, fields=True)
+                        else:
+                            dev = gpu_ctx.decode_host(dp, data, off, cap, layouts=layouts)
+                        assert_same(dev, ref_lay if layouts is True else ref, "%s/layouts=%s" % (what, layouts))
+                    # fused grouping keys (gpk_decode_group_batch): the decode's own outputs
+                    d = torch.from_numpy(data).cuda()
+                    o = torch.from_numpy(off.astype(np.int64)).cuda()
+                    c = torch.from_numpy(cap.astype(np.int32)).cuda()
+                    rec = torch.zeros(SELECTION_N * 16, dtype=torch.uint8, device="cuda")
+                    err = torch.zeros(2 * SELECTION_N, dtype=torch.int32, device="cuda")
+                    fl = torch.zeros(3 * SELECTION_N, dtype=torch.int64, device="cuda")
+                    grouper.decode_group(gpu_ctx, dp, d, o, c, rec, err, fl, kind=flows.CONNECTION)
+                    torch.cuda.synchronize()
+                    dev = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
+                               err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
+                               layouts=None)
+                    assert_same(dev, ref, what + "/keys")
+    finally:
+        gpu_ctx.set_table_mode(_lib.TABLES_AUTO)
+        grouper.close()

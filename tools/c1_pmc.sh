@@ -1,6 +1,8 @@
 # PMC A/B of the C1 kernels: the dword-aligned 5-chunk
 # window (AL = 4, the default) against the 16-byte-aligned 6-chunk window
-# (variant al16 = GPK_MID_W5=0), one pass per counter group.
+# (variant al16 = GPK_MID_W5=0), one pass per counter group. GPK_MID_W5 has
+# since been folded into select() (Knobs): the al16 variant
+# builds from commit 7727370 or earlier only.
 # Usage: [SQ=1] bash tools/c1_pmc.sh OUTDIR "variants" [config]   (SQ=1: wave/instruction/LDS passes too)
 set -o pipefail
 OUT=gpurun_out/$1; VARS=${2:-"base al16"}; CFG=${3:-c1}
