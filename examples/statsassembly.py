@@ -15,12 +15,19 @@ launch (DecodingLayerParser.DecodeBatch), and the per-packet loop is the
 reference's, over the layer structs as DecodeLayers leaves them (Hydrate).
 The streams' statistics stand in for statsStream's (main.go:52-99): packets,
 payload bytes, first and last capture time, and whether a SYN or a FIN/RST
-was seen. tcpassembly's reassembly itself is out of scope, so
-there are no out-of-order or skip counts.
+was seen. This default mode does not reassemble, so it has no out-of-order or
+skip counts; --device-assembly (below) does.
 
 --device-groups also forms the connection keys on the device
 (gpk_group_batch, GPK_GROUP_CONNECTION) and checks that they split the
 assembled packets exactly as the loop's keys do.
+
+--device-assembly runs tcpassembly itself on the device instead
+(gopacket_amd.tcpassembly, include/gpk_tcpasm.h): the statsStream objects of
+main.go:52-99 are fed the reassembled chunks batch by batch, FlushAll() follows
+the last batch (main.go:210), and the statistics gain the reference's
+out-of-order and skipped counts. Reassembly.Seen is the capture time of the
+chunk's source packet.
 
   python examples/statsassembly.py tests/golden/test_ethernet.pcap -v
 """
@@ -128,6 +135,92 @@ def run(path, count=-1, batch=1 << 16, verbose=False, device_groups=False, log=p
     return list(streams.values()), read, byte_count
 
 
+class DeviceStatsStream:
+    """statsStream (main.go:52-99) as a gopacket_amd.tcpassembly Stream. start
+    is the capture time of the first chunk (the reference takes time.Now() in
+    New, which a capture file cannot give)."""
+
+    def __init__(self, net, transport, log):
+        self.net, self.transport, self.log = net, transport, log
+        self.bytes = self.packets = self.outOfOrder = self.skipped = 0
+        self.start = self.end = None
+        self.sawStart = self.sawEnd = self.complete = False
+
+    def Reassembled(self, reassemblies):
+        for r in reassemblies:
+            if self.start is None:
+                self.start = self.end = r.Seen
+            if r.Seen < self.end:
+                self.outOfOrder += 1
+            else:
+                self.end = r.Seen
+            self.bytes += len(r.Bytes)
+            self.packets += 1
+            if r.Skip > 0:
+                self.skipped += r.Skip
+            self.sawStart = self.sawStart or r.Start
+            self.sawEnd = self.sawEnd or r.End
+
+    def ReassemblyComplete(self):
+        self.complete = True
+        secs = (self.end - self.start) if self.start is not None else 0
+        self.log("Reassembly of stream %s:%s complete - start:%s end:%s bytes:%d packets:%d ooo:%d bps:%s pps:%s "
+                 "skipped:%d" % (self.net, self.transport, "%.6f" % self.start if self.start is not None else "-",
+                                 "%.6f" % self.end if self.end is not None else "-", self.bytes, self.packets,
+                                 self.outOfOrder, "%.1f" % (self.bytes / secs) if secs > 0 else "+Inf",
+                                 "%.1f" % (self.packets / secs) if secs > 0 else "+Inf", self.skipped))
+
+
+def run_device_assembly(path, count=-1, batch=1 << 16, max_pages=0, log=print):
+    """main.go:119-211 with tcpassembly on the device. Returns (streams in the
+    order of their New calls, packets read, bytes of the packets decoded
+    without error)."""
+    import numpy as np
+    from gopacket_amd import _lib, gopacket, layers, pcapgo, tcpassembly
+    parser = gopacket.NewDecodingLayerParser(layers.LayerTypeEthernet, layers.Ethernet(), layers.Dot1Q(),
+                                             layers.IPv4(), layers.IPv6(), layers.IPv6ExtensionSkipper(), layers.TCP(),
+                                             gopacket.Payload())
+    made = []
+
+    class Factory(tcpassembly.StreamFactory):
+        def New(self, net, transport):
+            log("new stream %s:%s started" % (net, transport))
+            made.append(DeviceStatsStream(net, transport, log))
+            return made[-1]
+
+    assembler = tcpassembly.NewAssembler(tcpassembly.NewStreamPool(Factory()), ctx=parser.ctx(),
+                                         parser=parser._config(), max_packets=2 * batch + 1024)
+    assembler.MaxBufferedPagesPerConnection = max_pages
+    read = byte_count = 0
+    start = time.time()
+    with open(path, "rb") as f:
+        r = open_reader(f)
+        while count != 0:
+            try:
+                b = r.ReadBatch(batch if count < 0 else min(batch, count))
+            except pcapgo.EOFErrorGo:
+                break
+            except pcapgo.PcapgoError as e:
+                log("error getting packet: %s" % e)
+                break
+            read += len(b)
+            if count > 0:
+                count -= len(b)
+            pb = gopacket.PacketBatch(b.data, b.offsets, b.caplens)
+            res = parser.DecodeBatch(pb)
+            # the loop `continue`s on a decode error (main.go:179-182): those packets are not assembled
+            ok = np.flatnonzero((res.records["status"] & _lib.ST_ERR_MASK) == 0)
+            for i in np.flatnonzero((res.records["status"] & _lib.ST_ERR_MASK) != 0):
+                log("error decoding packet: %s" % res.Err(int(i)).Error())
+            byte_count += int(pb.caplens[ok].sum())
+            seen = b.ci["ts_sec"][ok].astype(np.float64) + b.ci["ts_nsec"][ok] * 1e-9
+            assembler.AssembleBatch(pb.data, pb.offsets[ok], pb.caplens[ok], seen)
+    assembler.FlushAll()
+    assembler.close()
+    log("processed %d bytes in %.3fs" % (byte_count, time.time() - start))
+    return made, read, byte_count
+
+
 def check_device_groups(parser, pb, assembled):
     """The same batch decoded and grouped on the device (gpk_group_batch,
     CONNECTION): every key of the loop must be exactly one device group and
@@ -165,7 +258,14 @@ def main():
     ap.add_argument("--batch", type=int, default=1 << 16, help="packets per DecodeBatch launch")
     ap.add_argument("--device-groups", action="store_true",
                     help="also group on the device (gpk_group_batch) and check it against the loop")
+    ap.add_argument("--device-assembly", action="store_true",
+                    help="reassemble the TCP streams on the device (gopacket_amd.tcpassembly)")
+    ap.add_argument("--max-pages", type=int, default=0,
+                    help="MaxBufferedPagesPerConnection for --device-assembly (0: no limit)")
     a = ap.parse_args()
+    if a.device_assembly:
+        run_device_assembly(a.file, a.c, a.batch, a.max_pages)
+        return
     run(a.file, a.c, a.batch, a.v, a.device_groups)
 
 

@@ -101,6 +101,8 @@ EXPORTS = (
     "gpk_bpf_create", "gpk_bpf_destroy", "gpk_bpf_run", "gpk_bpf_select",
     # include/gpk_defrag.h
     "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch",
+    # include/gpk_tcpasm.h
+    "gpk_tcpasm_create", "gpk_tcpasm_destroy", "gpk_tcpasm_batch",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -128,6 +130,35 @@ class Datagrams(ctypes.Structure):
                 ("offsets", ctypes.c_void_p), ("caplens", ctypes.c_void_p), ("payload_off", ctypes.c_void_p),
                 ("pending", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("data", ctypes.c_void_p),
                 ("data_cap", ctypes.c_uint64)]
+
+
+# include/gpk_tcpasm.h constants
+TCPASM_DIRECT, TCPASM_QUEUED, TCPASM_NOCONN, TCPASM_CARRIED, TCPASM_EBADCARRY, TCPASM_EPANIC = \
+    -24, -25, -26, -27, -28, -29
+TCPASM_PAGE_BYTES = 1900
+TCP_START, TCP_END = 1, 2
+TCPASM_CALL_FLUSH, TCPASM_OPEN, TCPASM_NO_CONN = 0x80000000, 0xFFFFFFFF, -2
+TCPASM_CARRY_CONN, TCPASM_CARRY_PAGE = 0x80000000, 0x40000000
+# gpk_tcp_chunk (40 B): one Reassembly
+TCP_CHUNK_DTYPE = np.dtype([("dst", "<u8"), ("skip", "<i8"), ("src", "<u4"), ("src_off", "<u4"), ("len", "<u4"),
+                            ("call", "<u4"), ("stream", "<u4"), ("flags", "<u4")])
+
+
+class TcpasmOpts(ctypes.Structure):
+    """gpk_tcpasm_opts"""
+    _fields_ = [("max_pages", ctypes.c_uint32), ("flush", ctypes.c_uint32), ("carried", ctypes.c_uint64),
+                ("carry_code", ctypes.c_void_p), ("carry_seq", ctypes.c_void_p)]
+
+
+class TcpStreams(ctypes.Structure):
+    """gpk_tcp_streams: the outputs of gpk_tcpasm_batch (device arrays)."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("stream_of", ctypes.c_void_p), ("chunks", ctypes.c_void_p),
+                ("stream_group", ctypes.c_void_p), ("stream_first", ctypes.c_void_p),
+                ("stream_closed", ctypes.c_void_p), ("stream_chunk0", ctypes.c_void_p),
+                ("stream_data0", ctypes.c_void_p), ("conn_seq", ctypes.c_void_p), ("conn_stream", ctypes.c_void_p),
+                ("pend_pkt", ctypes.c_void_p), ("pend_page", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("data", ctypes.c_void_p), ("chunk_cap", ctypes.c_uint64), ("data_cap", ctypes.c_uint64)]
+
 
 # include/gpk_afpacket.h constants
 TPACKET_V1, TPACKET_V2, TPACKET_V3, TPACKET_HIGHEST = 0, 1, 2, -1
@@ -370,6 +401,9 @@ def lib():
         "gpk_defragger_create": ([P(vp), c_int, u64], c_int),
         "gpk_defragger_destroy": ([vp], c_int),
         "gpk_defrag_batch": ([vp, P(Batch), P(Results), P(Groups), P(Datagrams), vp], c_int),
+        "gpk_tcpasm_create": ([P(vp), c_int, u64], c_int),
+        "gpk_tcpasm_destroy": ([vp], c_int),
+        "gpk_tcpasm_batch": ([vp, P(Batch), P(Results), P(Groups), P(TcpasmOpts), P(TcpStreams), vp], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

@@ -17,6 +17,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            ip4defrag's reassembly of a DEFRAG-grouped
                                            batch (defrag.go:113-132,214-326)
   IPv4Defragmenter(ctx, parser, n)         the same over a stream of batches
+  Assembler(max_packets).assemble(...)     gpk_tcpasm_batch (include/gpk_tcpasm.h):
+                                           tcpassembly's reassembly of a CONNECTION-grouped
+                                           batch (assembly.go:536-783, FlushAll :279-290)
+  TCPAssembler(ctx, parser, n)             the same over a stream of batches
 """
 import ctypes
 
@@ -259,3 +263,247 @@ class IPv4Defragmenter:
     def close(self):
         self.grouper.close()
         self.defragmenter.close()
+
+
+DIRECT, QUEUED, NOCONN, CARRIED, EBADCARRY, TCP_EPANIC = (
+    _lib.TCPASM_DIRECT, _lib.TCPASM_QUEUED, _lib.TCPASM_NOCONN, _lib.TCPASM_CARRIED, _lib.TCPASM_EBADCARRY,
+    _lib.TCPASM_EPANIC)
+
+
+class Assembler:
+    """gpk_tcpasm_batch (include/gpk_tcpasm.h): the Reassembly objects
+    tcpassembly's Assembler would have handed every stream of a decoded,
+    CONNECTION-grouped batch, the streams' bytes, every packet's verdict and
+    the state at the end. One call behaves like a fresh NewAssembler with
+    MaxBufferedPagesPerConnection = max_pages fed the batch in order, then
+    FlushAll() if `flush`. No timestamps (FlushOlderThan)."""
+
+    def __init__(self, max_packets, device=0):
+        self.h = ctypes.c_void_p()
+        _lib.check(_lib.lib().gpk_tcpasm_create(ctypes.byref(self.h), device, int(max_packets)))
+        self.max_packets = int(max_packets)
+
+    def assemble(self, data, offsets, caplens, records, layouts, groups, max_pages=0, flush=False, data_cap=None,
+                 stream=None, chunk_cap=None, out_data=None, carry_code=None, carry_seq=None):
+        """Device tensors in: the batch, its records and layouts, and `groups`
+        (Grouper.group(kind=CONNECTION) of it). Returns a dict of device tensors:
+        verdict[n], stream_of[n], chunks (uint8 view of gpk_tcp_chunk[chunk_cap],
+        _lib.TCP_CHUNK_DTYPE on the host), stream_group/first/closed[n],
+        stream_chunk0/stream_data0[n+1], conn_seq/conn_stream[n] (per group),
+        pend_pkt/pend_page[chunk_cap], counts[8] and data. chunk_cap defaults to
+        n + data bytes / 1900 and data_cap to the batch's data size, which always
+        suffice. carry_code (int32 bit patterns) / carry_seq (int64): the first
+        carry_code.numel() packets are carried entries."""
+        import torch
+        n = offsets.numel()
+        dev = offsets.device
+        if out_data is None:
+            cap = int(data.numel() if data_cap is None else data_cap)
+            out_data = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
+        else:
+            cap = int(out_data.numel() if data_cap is None else data_cap)
+        ccap = int(n + data.numel() // _lib.TCPASM_PAGE_BYTES if chunk_cap is None else chunk_cap)
+        m, cm = max(n, 1), max(ccap, 1)
+        i32, i64 = torch.int32, torch.int64
+        out = dict(verdict=torch.empty(m, dtype=i32, device=dev), stream_of=torch.empty(m, dtype=i32, device=dev),
+                   chunks=torch.empty(cm * 40, dtype=torch.uint8, device=dev),
+                   stream_group=torch.empty(m, dtype=i32, device=dev),
+                   stream_first=torch.empty(m, dtype=i32, device=dev),
+                   stream_closed=torch.empty(m, dtype=i32, device=dev),
+                   stream_chunk0=torch.empty(m + 1, dtype=i32, device=dev),
+                   stream_data0=torch.empty(m + 1, dtype=i64, device=dev),
+                   conn_seq=torch.empty(m, dtype=i64, device=dev), conn_stream=torch.empty(m, dtype=i32, device=dev),
+                   pend_pkt=torch.empty(cm, dtype=i32, device=dev), pend_page=torch.empty(cm, dtype=i32, device=dev),
+                   counts=torch.zeros(8, dtype=i64, device=dev), data=out_data)
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        g = _lib.Groups(groups["group_of"].data_ptr(), groups["perm"].data_ptr(), groups["start"].data_ptr(),
+                        groups["first"].data_ptr(), groups["counts"].data_ptr())
+        carried = 0 if carry_code is None else int(carry_code.numel())
+        op = _lib.TcpasmOpts(int(max_pages), 1 if flush else 0, carried,
+                             carry_code.data_ptr() if carried else None, carry_seq.data_ptr() if carried else None)
+        o = _lib.TcpStreams(*[out[k].data_ptr() for k in (
+            "verdict", "stream_of", "chunks", "stream_group", "stream_first", "stream_closed", "stream_chunk0",
+            "stream_data0", "conn_seq", "conn_stream", "pend_pkt", "pend_page", "counts")], out_data.data_ptr(), ccap,
+            cap)
+        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        _lib.check(_lib.lib().gpk_tcpasm_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                               ctypes.byref(op), ctypes.byref(o), sp))
+        out["verdict"], out["stream_of"] = out["verdict"][:n], out["stream_of"][:n]
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().gpk_tcpasm_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TCPAssembler:
+    """A streaming tcpassembly.Assembler over device batches. The open
+    connections and the pages still listed after a batch stay on the device
+    (pack_batch of their packets) and go in front of the next batch as carried
+    entries, which reproduces the reference's state. Stream ids are global over
+    the calls; a source packet or call is (batch number, index), batch numbers
+    counting assemble() calls from 0. max_packets bounds carried entries plus
+    batch; the workspaces are rebuilt larger when open connections outgrow it.
+    No timeouts: flush_all() is FlushAll()."""
+
+    def __init__(self, ctx, parser, max_packets, max_pages=0, device=0, keys=False):
+        self.ctx, self.parser = ctx, parser
+        self.max_packets, self.max_pages = int(max_packets), int(max_pages)
+        self.keys = keys  # also return every new stream's key (its flows' bytes)
+        self.device = device
+        self.grouper = Grouper(self.max_packets, device)
+        self.assembler = Assembler(self.max_packets, device)
+        self._carry = None  # (data, offsets, caplens, code[], seq[], gid[], origin[(batch, index)])
+        self._streams = 0   # global ids handed out so far
+        self._batch = 0
+
+    @property
+    def open_count(self):
+        return 0 if self._carry is None else sum(1 for c in self._carry[3] if c & _lib.TCPASM_CARRY_CONN)
+
+    def flush_all(self):
+        """FlushAll(): a carried-only call with flush. Returns assemble()'s result."""
+        import torch
+        dev = torch.device("cuda", torch.cuda.current_device()) if self._carry is None else self._carry[1].device
+        e = torch.empty(0, dtype=torch.uint8, device=dev)
+        return self._run(e, torch.empty(0, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev), True, False)
+
+    def assemble(self, data, offsets, caplens):
+        """One batch (device tensors: uint8 data, int64 offsets, int32 caplens).
+        Returns dict(verdict, stream_of (global ids, per caller's packet),
+        streams: [dict(id, new, closed, chunks: [dict(src, src_off, len, skip,
+        call, flags, dst)], data0, data1)], data (device), counts). src and call
+        are (batch, index); a flush call is ("flush", round). With keys=True a
+        new stream also has key = (net type 4 or 6, src, dst, sport, dport) as
+        bytes, from its creating packet."""
+        return self._run(data, offsets, caplens, False, True)
+
+    def _run(self, data, offsets, caplens, flush, count_batch):
+        import numpy as np
+        import torch
+        dev = offsets.device
+        P = 0 if self._carry is None else len(self._carry[3])
+        code = seq = None
+        if P:
+            pd, po, pc, ccode, cseq, cgid, corigin = self._carry
+            base = pd.numel()
+            # 16 spare bytes: the byte mover's aligned loads may reach past the last payload
+            data = torch.cat([pd, data, torch.zeros(16, dtype=torch.uint8, device=dev)])
+            offsets = torch.cat([po, offsets + base])
+            caplens = torch.cat([pc, caplens])
+            code = torch.tensor(np.array(ccode, dtype=np.uint32).view(np.int32), dtype=torch.int32, device=dev)
+            seq = torch.tensor(cseq, dtype=torch.int64, device=dev)
+        else:
+            cgid, corigin = [], []
+        n = offsets.numel()
+        if n > self.max_packets:  # open connections accumulate: the workspaces grow with them
+            self.close()
+            self.max_packets = max(n, 2 * self.max_packets)
+            self.grouper = Grouper(self.max_packets, self.device)
+            self.assembler = Assembler(self.max_packets, self.device)
+        bno = self._batch
+        if count_batch:
+            self._batch += 1
+        if n == 0:
+            return dict(verdict=[], stream_of=[], streams=[], data=torch.empty(0, dtype=torch.uint8, device=dev),
+                        counts=[0] * 8)
+        rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+        flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream()
+        self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
+        groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=CONNECTION, stream=st)
+        out = self.assembler.assemble(data, offsets, caplens, rec, lay, groups, max_pages=self.max_pages, flush=flush,
+                                      stream=st, carry_code=code, carry_seq=seq)
+        counts = out["counts"].cpu().tolist()
+        S, C, NP = counts[0], counts[1], counts[3]
+        G = int(groups["counts"][0].item())
+        chunks = out["chunks"].cpu().numpy().view(_lib.TCP_CHUNK_DTYPE)[:C]
+        first = out["stream_first"][:S].cpu().tolist()
+        closed = out["stream_closed"][:S].cpu().numpy().view(np.uint32).tolist()
+        chunk0 = out["stream_chunk0"][:S + 1].cpu().tolist()
+        data0 = out["stream_data0"][:S + 1].cpu().tolist()
+
+        def origin(i):
+            return corigin[i] if i < P else (bno, i - P)
+
+        def call(c):
+            return ("flush", c & 0x7FFFFFFF) if c & _lib.TCPASM_CALL_FLUSH else origin(c)
+
+        ids, streams = [], []
+        for j in range(S):
+            new = first[j] >= P
+            if new:
+                ids.append(self._streams)
+                self._streams += 1
+            else:
+                ids.append(cgid[first[j]])
+            ch = [dict(src=origin(int(c["src"])), src_off=int(c["src_off"]), len=int(c["len"]), skip=int(c["skip"]),
+                       call=call(int(c["call"])), flags=int(c["flags"]), dst=int(c["dst"]))
+                  for c in chunks[chunk0[j]:chunk0[j + 1]]]
+            streams.append(dict(id=ids[j], new=new, first=origin(first[j]), closed=None if closed[j] == _lib.TCPASM_OPEN else call(closed[j]),
+                                chunks=ch, data0=data0[j], data1=data0[j + 1]))
+        if self.keys:
+            new = [j for j in range(S) if streams[j]["new"]]
+            if new:
+                fi = torch.tensor([first[j] for j in new], dtype=torch.int32, device=dev)
+                hd, ho, _ = pack_batch(data, offsets, caplens, fi, stream=st)
+                hd, ho = hd.cpu().numpy(), ho.cpu().tolist()
+                starts = lay.view(torch.int32).view(n, 16).index_select(0, fi.long())[:, :8].cpu().tolist()
+                for j, at, ls in zip(new, ho, starts):
+                    ip4, ip6, tcp = ls[2], ls[3], ls[5]  # gpk_layout slots; -1 = absent
+                    six = ip6 >= 0 and ip6 < tcp and not (ip4 >= 0 and ip6 < ip4 < tcp)
+                    a = at + (ip6 + 8 if six else ip4 + 12)
+                    w = 16 if six else 4
+                    t = at + tcp
+                    streams[j]["key"] = (6 if six else 4, hd[a:a + w].tobytes(), hd[a + w:a + 2 * w].tobytes(),
+                                         hd[t:t + 2].tobytes(), hd[t + 2:t + 4].tobytes())
+        so = out["stream_of"][P:].cpu().tolist()
+        result = dict(verdict=out["verdict"][P:].cpu().tolist(), stream_of=[ids[x] if x >= 0 else -1 for x in so],
+                      streams=streams, data=out["data"], counts=counts)
+        # the state for the next call: per open connection its key's first packet
+        # (CARRY_CONN), then its listed pages in list order (CARRY_PAGE | page)
+        conn_seq = out["conn_seq"][:G].cpu().tolist()
+        conn_stream = out["conn_stream"][:G].cpu().tolist()
+        gfirst = groups["first"][:G].cpu().tolist()
+        group_of = groups["group_of"].cpu().tolist()
+        pend_pkt, pend_page = out["pend_pkt"][:NP].cpu().tolist(), out["pend_page"][:NP].cpu().tolist()
+        order, ncode, nseq, ngid, norigin = [], [], [], [], []
+        pages = {}
+        for p, k in zip(pend_pkt, pend_page):
+            pages.setdefault(group_of[p], []).append((p, k))
+        for g in range(G):
+            if conn_seq[g] == _lib.TCPASM_NO_CONN:
+                continue
+            order.append(gfirst[g])
+            ncode.append(_lib.TCPASM_CARRY_CONN)
+            nseq.append(conn_seq[g])
+            ngid.append(ids[conn_stream[g]])
+            norigin.append(origin(gfirst[g]))
+            for p, k in pages.get(g, ()):
+                order.append(p)
+                ncode.append(_lib.TCPASM_CARRY_PAGE | k)
+                nseq.append(0)
+                ngid.append(ids[conn_stream[g]])
+                norigin.append(origin(p))
+        if order:
+            ot = torch.tensor(order, dtype=torch.int32, device=dev)
+            total = int(caplens.index_select(0, ot.long()).sum(dtype=torch.int64).item())
+            d2, o2, c2 = pack_batch(data, offsets, caplens, ot, total_bytes=total, stream=st)
+            self._carry = (d2[:total], o2, c2, ncode, nseq, ngid, norigin)
+        else:
+            self._carry = None
+        return result
+
+    def close(self):
+        self.grouper.close()
+        self.assembler.close()
