@@ -29,6 +29,10 @@
 //      is all the fold needs; see l_to_words). No per-packet reduction.
 //    * sparse waves (scattered offsets): the segments are streamed one after
 //      another as whole-wave 1 KiB loads and reduced per packet (DPP).
+//  Two launches run phase B's stream before phase A, over the packets' extents:
+//  decode_sb_kernel (small packets: windows by LDS-DMA, then the stream) and
+//  the big-packet L4 specialisation of decode_kernel (decode_sw_body: the
+//  windows are taken out of the stream itself, every byte read once).
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -763,9 +767,26 @@ struct SbPkt {
 // The stream of a stream-before-parse wave: region [R0, R0 + R), D passes in
 // flight (the dense stream's slots and waits); returns P(b) - P(a1) for the
 // lane's packet (a1 = -1: none before it).
-template <int D>
+//
+// kWin (decode_kernel's big-packet L4 body): the stream also leaves every
+// packet's header window in LDS, so no packet byte is fetched twice. Lane q's
+// window is granules [h, h + nch) of the region (h = (wb - R0) >> 4,
+// non-decreasing in lane order: the caller checked the offsets); a window cell
+// is one granule, so in each pass, once its slot has landed and before the
+// refill, the lanes holding granules of packet q's window store their 16 bytes
+// to cell 64 p + lane - h of slot q (`cells`: the wave's first slot, a dword
+// index). A scalar cursor (wq, its h and nch in wh / wn; wh = ~0: no packet
+// left) walks the packets whose windows start inside the pass; it stays on the
+// first one whose window reaches into the next pass, and the packets behind it
+// are walked again there (their cells of this pass match no lane then). A
+// granule inside several windows (short packets) is stored once per owner. A
+// pass no window starts or continues in pays one scalar compare; a 1500-byte
+// packet's wave makes 64 stores in its 94 passes. Wave-uniform throughout: no
+// atomics, no waiting on another wave.
+template <int D, bool kWin = false>
 __device__ __forceinline__ uint32_t sb_stream(const KParams& P, Stream<D>& S, uint64_t R0, uint32_t R, uint32_t lane,
-                                              int32_t a1, int32_t b) {
+                                              int32_t a1, int32_t b, uint32_t h = 0, uint32_t nch = 0,
+                                              uint32_t cells = 0) {
   stream_issue(P, S, R0, R, lane, 0, D);
   const __amdgpu_buffer_rsrc_t rs = rsrc(P.data + R0, (R + 15) & ~15u);
   const uint32_t np = (R + kPassBytes - 1) / kPassBytes;  // wave-uniform
@@ -774,8 +795,38 @@ __device__ __forceinline__ uint32_t sb_stream(const KParams& P, Stream<D>& S, ui
   const int32_t pa = a1 >> 6, pb = b >> 6;  // -1 never matches
   const int32_t la = (a1 & 63) << 2, lb = (b & 63) << 2, ll = (int32_t)lane << 2;
   uint32_t xa = 0, xb = 0, c = 0;
+  uint32_t wq = 0, wh = kWin ? readlane32(h, 0) : ~0u, wn = kWin ? readlane32(nch, 0) : 0u;
   auto pass = [&](const int d, const int32_t p, const bool refill) __attribute__((always_inline)) {
     const uint32_t gl = chunk_l(ring[d], 0u);
+    if (kWin) {
+      const uint32_t g0 = (uint32_t)p << 6, g1 = g0 + 64;  // the pass holds granules [g0, g1)
+      if (wh < g1) {
+        uint32_t j = wq, hj = wh, nj = wn;
+        bool carried = false;
+        do {
+          // the lane's granule as a cell of packet j (wraps below its window); the scalar parts stay scalar
+          // (opaque: folded into per-pass vector addresses they cost a register per unrolled pass)
+          uint32_t dg = g0 - hj, cj = cells + j * (4 * kWinChunks);
+          asm volatile("" : "+s"(dg), "+s"(cj));
+          const uint32_t rel = lane + dg;
+          if (rel < nj) *reinterpret_cast<u32x4*>(gpk_smem + cj + rel * 4) = ring[d];
+          if (!carried && hj + nj > g1) {  // the rest of this window is in the next pass
+            carried = true;
+            wq = j;
+            wh = hj;
+            wn = nj;
+          }
+          j++;
+          hj = j < 64 ? readlane32(h, j & 63) : ~0u;
+          nj = readlane32(nch, j & 63);
+        } while (hj < g1);
+        if (!carried) {
+          wq = j;
+          wh = hj;
+          wn = nj;
+        }
+      }
+    }
     if (refill) slot_load(ring[d], rs, vo, (uint32_t)(p + D) * kPassBytes);
     const uint32_t sc = wave_scan(gl);
     const uint32_t Pf = sc + c;
@@ -1201,10 +1252,21 @@ __device__ __forceinline__ void diag_store(const KParams& P, uint64_t (&dt)[8], 
 // (mean < 1 KiB) are issue-bound in the header phase and run O = 7 (72 VGPRs;
 // with the table blob sized to the parser, 7 blocks fit a CU's LDS); big
 // packets keep O = 6.
+// The big-packet L4 launch (6-chunk window, O = 6, no layouts, no keys) keeps
+// this kernel's name and runs decode_sw_body (below): index, stream, parse,
+// correction, stores, every packet byte read once.
+template <bool kCompact, int W, int O>
+__device__ __forceinline__ void decode_sw_body(const KParams& P);
+
 template <bool kL4, bool kLayout, bool kCompact, bool kKeys = false, int W = kWinChunks, int O = GPK_WAVES_PER_EU,
           int AL = 16>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(W == 4 ? GPK_W4_WAVES : O, 8))) void decode_kernel(
     KParams P) {
+  if constexpr (kL4 && !kLayout && !kKeys && W == kWinChunks && O == GPK_WAVES_PER_EU && AL == 16 &&
+                slot_dw_of<W, AL>() == 4 * W) {
+    decode_sw_body<kCompact, W, O>(P);
+    return;
+  }
   const uint32_t tid = threadIdx.x;
   const uint32_t slot_dw = tid * slot_dw_of<W, AL>();
   const uint32_t base = kBlock * slot_dw_of<W, AL>();
@@ -1351,6 +1413,87 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(O, 8))) 
   else
     decode_packet<true, false, GTab, false, W, O, 16, kSbStride, 0, true, kFields>(
         P, GTab{P.tab}, i1, i1 < P.n, c1.off, c1.cl, g1, tid1 * kSbStride, tid1 & 63, dt, SbPkt{L, R0, b, ok});
+#if GPK_DIAG_TIMES
+  dt[7] = ok ? (uint64_t)R | (uint64_t)__builtin_popcountll(__ballot(active)) << 32 : 0;
+  diag_store(P, dt, wave, lane);
+#endif
+}
+
+// The body of decode_kernel's big-packet L4 specialisation: every packet byte
+// is read exactly once. The stream over the wave's packets starts right behind
+// the index and leaves the header windows in LDS on its way (sb_stream, kWin):
+// no window load, no dependent round trip before the stream, no second fetch
+// of a packet's head line. Slots are decode_sb_kernel's (six 16-byte cells per
+// packet, no pad: a cell is one stream granule). A wave takes this order when
+// its packets are packed (dense_region over the extents) and their offsets do
+// not decrease in lane order (lanes past the batch repeat the last entry);
+// any other wave loads its windows (window_dma) and runs phase B after the
+// parse, with the same results.
+template <bool kCompact, int W, int O>
+__device__ __forceinline__ void decode_sw_body(const KParams& P) {
+  constexpr int D = GPK_PB_DEPTH;
+  constexpr int kStride = 4 * W;  // one 16-byte cell per window chunk, no pad
+  const uint32_t tid = threadIdx.x, lane = tid & 63;
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const uint32_t base = kBlock * kStride;  // table blob (dwords)
+  if ((uint64_t)blockIdx.x * kBlock >= P.n) return;  // uniform over the block
+  const uint64_t i0 = (uint64_t)blockIdx.x * kBlock + tid;
+  const bool active = i0 < P.n;
+  uint64_t dt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#if GPK_DIAG_TIMES
+  dt[0] = __builtin_amdgcn_s_memrealtime();
+#endif
+  const Idx c0 = load_index(P, i0);
+  const WinGeo g0 = win_geo<W, 16>(P, c0, active);
+  if (kCompact) {  // the table blob (read after the barrier below)
+    static_assert(kCtDwords <= 3 * kBlock, "three blob words per thread");
+    const uint32_t last = P.cg.words - 1;
+#pragma unroll
+    for (uint32_t k = 0; k < 3; k++) {
+      const uint32_t j = tid + k * kBlock < last ? tid + k * kBlock : last;
+      gpk_smem[base + j] = P.ctab[j];
+    }
+  }
+#if GPK_DIAG_TIMES
+  dt[1] = __builtin_amdgcn_s_memrealtime();  // (diag phases: index | stream | parse | correction)
+#endif
+  uint64_t R0 = 0;
+  uint32_t R = 0;
+  bool ok = dense_region(active && (P.outputs & GPK_OUT_L4_CSUM) != 0, c0.off, c0.off + c0.cl, R0, R);
+  const uint32_t noff_lo = (uint32_t)__shfl_down((int)(uint32_t)c0.off, 1);
+  const uint32_t noff_hi = (uint32_t)__shfl_down((int)(uint32_t)(c0.off >> 32), 1);
+  ok = ok && !__ballot(lane < 63 && ((uint64_t)noff_hi << 32 | noff_lo) < c0.off);
+  uint32_t L = 0;
+  int32_t b = -1;
+  if (ok) {
+    const uint32_t h = (uint32_t)((g0.wb - R0) >> 4);
+    const int32_t a1 = active ? (int32_t)h - 1 : -1;
+    b = active ? (int32_t)(((c0.off + c0.cl) - 1 - R0) >> 4) : -1;
+    Stream<D> S;
+    S.on = true;
+    L = sb_stream<D, true>(P, S, R0, R, lane, a1, b, h, g0.nch, wave * (64u * kStride));
+  } else {
+    window_dma<W>(P, g0, (uint32_t)(uintptr_t)gpk_smem + wave * (64u * kStride * 4u), lane);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the windows have landed
+  }
+  // (the block's barrier before the stream instead measured the same to +0.8 %: profiles/ab_stream_windows.txt)
+  if (kCompact) __syncthreads();
+#if GPK_DIAG_TIMES
+  dt[2] = __builtin_amdgcn_s_memrealtime();
+#endif
+  // only the index entry crosses the stream: everything derived from it is formed again
+  uint32_t off_lo = (uint32_t)c0.off, off_hi = (uint32_t)(c0.off >> 32), ccl = c0.cl;
+  asm volatile("" : "+v"(off_lo), "+v"(off_hi), "+v"(ccl));
+  const Idx c1{(uint64_t)off_hi << 32 | off_lo, ccl};
+  const uint32_t tid1 = threadIdx.x;
+  const uint64_t i1 = (uint64_t)blockIdx.x * kBlock + tid1;
+  const WinGeo g1 = win_geo<W, 16>(P, c1, i1 < P.n);
+  if (kCompact)
+    decode_packet<true, false, LTab, false, W, O, 16, kStride, 0, true>(
+        P, LTab{P.cg, base}, i1, i1 < P.n, c1.off, c1.cl, g1, tid1 * kStride, tid1 & 63, dt, SbPkt{L, R0, b, ok});
+  else
+    decode_packet<true, false, GTab, false, W, O, 16, kStride, 0, true>(
+        P, GTab{P.tab}, i1, i1 < P.n, c1.off, c1.cl, g1, tid1 * kStride, tid1 & 63, dt, SbPkt{L, R0, b, ok});
 #if GPK_DIAG_TIMES
   dt[7] = ok ? (uint64_t)R | (uint64_t)__builtin_popcountll(__ballot(active)) << 32 : 0;
   diag_store(P, dt, wave, lane);
