@@ -103,6 +103,10 @@ EXPORTS = (
     "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch",
     # include/gpk_tcpasm.h
     "gpk_tcpasm_create", "gpk_tcpasm_destroy", "gpk_tcpasm_batch",
+    # include/gpk_capwrite.h
+    "gpk_capwriter_create", "gpk_capwriter_destroy", "gpk_capwriter_interfaces", "gpk_capwriter_set_interfaces",
+    "gpk_capwrite_file_header", "gpk_capwrite_section_header", "gpk_capwrite_add_interface",
+    "gpk_capwrite_interface_stats", "gpk_capwrite_secrets", "gpk_capwrite_batch", "gpk_capwrite_batch_host",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -158,6 +162,39 @@ class TcpStreams(ctypes.Structure):
                 ("stream_data0", ctypes.c_void_p), ("conn_seq", ctypes.c_void_p), ("conn_stream", ctypes.c_void_p),
                 ("pend_pkt", ctypes.c_void_p), ("pend_page", ctypes.c_void_p), ("counts", ctypes.c_void_p),
                 ("data", ctypes.c_void_p), ("chunk_cap", ctypes.c_uint64), ("data_cap", ctypes.c_uint64)]
+
+
+# include/gpk_capwrite.h constants
+CAPW_PCAP_MICRO, CAPW_PCAP_NANO, CAPW_PCAPNG = 1, 2, 3
+CAPW_OK, CAPW_ELENGTH, CAPW_EIFACE, CAPW_EBIG, CAPW_EINDEX, CAPW_ESECRETS = 0, -32, -33, -34, -35, -36
+CAPW_ZERO_TIME_SEC = -62135596800  # time.Time{}.Unix()
+
+
+class CapwBytes(ctypes.Structure):
+    _fields_ = [("data", ctypes.c_void_p), ("len", ctypes.c_uint64)]
+
+
+class CapwSection(ctypes.Structure):
+    _fields_ = [("application", CapwBytes), ("comment", CapwBytes), ("hardware", CapwBytes), ("os", CapwBytes)]
+
+
+class CapwInterface(ctypes.Structure):
+    _fields_ = [("name", CapwBytes), ("comment", CapwBytes), ("description", CapwBytes), ("filter", CapwBytes),
+                ("os", CapwBytes), ("ts_offset", ctypes.c_uint64), ("snap_length", ctypes.c_uint32),
+                ("link_type", ctypes.c_uint16), ("reserved", ctypes.c_uint16)]
+
+
+class CapwStats(ctypes.Structure):
+    _fields_ = [("last_update_sec", ctypes.c_int64), ("start_time_sec", ctypes.c_int64),
+                ("end_time_sec", ctypes.c_int64), ("last_update_nsec", ctypes.c_uint32),
+                ("start_time_nsec", ctypes.c_uint32), ("end_time_nsec", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("packets_received", ctypes.c_uint64),
+                ("packets_dropped", ctypes.c_uint64)]
+
+
+class CapwriteOpts(ctypes.Structure):
+    """gpk_capwrite_opts"""
+    _fields_ = [("now_sec", ctypes.c_int64), ("now_nsec", ctypes.c_uint32), ("group", ctypes.c_uint32)]
 
 
 # include/gpk_afpacket.h constants
@@ -404,6 +441,18 @@ def lib():
         "gpk_tcpasm_create": ([P(vp), c_int, u64], c_int),
         "gpk_tcpasm_destroy": ([vp], c_int),
         "gpk_tcpasm_batch": ([vp, P(Batch), P(Results), P(Groups), P(TcpasmOpts), P(TcpStreams), vp], c_int),
+        "gpk_capwriter_create": ([P(vp), c_int, c_int, u64], c_int),
+        "gpk_capwriter_destroy": ([vp], c_int),
+        "gpk_capwriter_interfaces": ([vp], c_int),
+        "gpk_capwriter_set_interfaces": ([vp, u32], c_int),
+        "gpk_capwrite_file_header": ([vp, u32, u32, vp, u64], c_int),
+        "gpk_capwrite_section_header": ([vp, P(CapwSection), vp, u64], c_int),
+        "gpk_capwrite_add_interface": ([vp, P(CapwInterface), vp, u64, P(c_int)], c_int),
+        "gpk_capwrite_interface_stats": ([vp, i64, P(CapwStats), vp, u64], c_int),
+        "gpk_capwrite_secrets": ([vp, u32, vp, u64, vp, u64], c_int),
+        "gpk_capwrite_batch": ([vp, P(Batch), vp, u64, vp, vp, vp, P(CapwriteOpts), vp, u64, vp, vp, vp, vp], c_int),
+        "gpk_capwrite_batch_host": ([vp, P(Batch), vp, u64, vp, vp, vp, P(CapwriteOpts), vp, u64, vp, vp, vp],
+                                    c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

@@ -15,6 +15,18 @@ Mirrors the reference's pcapgo package for the ingest side of the path
                                                   place in one staging buffer, ready
                                                   for DecodingLayerParser.DecodeBatch
 
+The writer half (include/gpk_capwrite.h):
+
+  NewWriter(w) / NewWriterNanos(w) -> Writer      pcapgo/write.go:53-76
+  Writer.WriteFileHeader(snaplen, linktype)       write.go:80-96
+  Writer.WritePacket(ci, data)                    write.go:117-129
+  NewNgWriter(w, linkType) / NewNgWriterInterface(w, intf, options) -> NgWriter
+                                                  ngwrite.go:56-79
+  NgWriter.AddInterface, WriteInterfaceStats, WritePacket, WritePacketWithOptions,
+  WriteDecryptionSecretsBlock, Flush              ngwrite.go:237-416, ngwrite_dsb.go:71-110
+  writer.WritePackets(device batch, ...)          the batch form: the packets are framed
+                                                  by the HIP kernels of gpk_capwrite.hip
+
 Every record is walked by libgpk's C++ indexer; errors are raised as
 PcapgoError carrying the reference's error text (io.EOF is "EOF", raised as
 EOFError subclass so `except EOFError` reads like Go's `err == io.EOF`).
@@ -136,6 +148,10 @@ class NgEpbFlags:
     Reception: int = 0
     FCSLen: int = 0
     LinkLayerErr: int = 0
+
+    def ToUint32(self):  # pcapng.go:165-172
+        return ((self.Direction & NgEpbFlagDirectionMask) | (self.Reception & NgEpbFlagReceptionTypeMask)
+                | (self.FCSLen & NgEpbFlagFCSLengthMask) | (self.LinkLayerErr & NgEpbFlagLinkLayerDependentErrorMask))
 
     @classmethod
     def FromUint32(cls, v):  # pcapng.go:174-179
@@ -570,3 +586,346 @@ def NewNgReader(r, options=DefaultNgReaderOptions):
 
 def NewReader(r):
     return Reader(r)
+
+
+# ---------------------------------------------------------------- writers
+ZeroTime = (_lib.CAPW_ZERO_TIME_SEC, 0)  # time.Time{}: (Unix seconds, nanoseconds)
+NgNoValue64 = (1 << 64) - 1
+DSB_SECRETS_TYPE_TLS, DSB_SECRETS_TYPE_SSH, DSB_SECRETS_TYPE_WIREGUARD = 0x544c534b, 0x5353484b, 0x57474b4c
+DSB_SECRETS_TYPE_ZIGBEE_NWK_KEY, DSB_SECRETS_TYPE_ZIGBEE_APS_KEY = 0x5a4e574b, 0x5a415053
+ErrUnknownSecretsType = "Unknown Decryption Secrets Block (DSB) type"
+ngEmptyStatistics = NgInterfaceStatistics(ZeroTime, ZeroTime, ZeroTime, b"", NgNoValue64, NgNoValue64)
+
+
+@dataclass
+class NgWriterOptions:  # ngwrite.go:22-25
+    SectionInfo: NgSectionInfo
+
+
+# runtime.GOARCH / runtime.GOOS of the machines this runs on; both can be set
+DefaultNgWriterOptions = NgWriterOptions(NgSectionInfo(Hardware=b"amd64", OS=b"linux", Application=b"gopacket",
+                                                       Comment=b""))
+DefaultNgInterface = NgInterface(Name=b"intf0", Comment=b"", Description=b"", Filter=b"", OS=b"linux", LinkType=0,
+                                 TimestampResolution=9, TimestampOffset=0, SnapLength=0,
+                                 Statistics=ngEmptyStatistics)
+
+
+def _b(v):
+    return v.encode() if isinstance(v, str) else bytes(v or b"")
+
+
+def _go_time(ts):
+    """Time.String() of time.Unix(sec, nsec).UTC()."""
+    import datetime
+    sec, nsec = int(ts[0]) + int(ts[1]) // 1000000000, int(ts[1]) % 1000000000
+    try:
+        t = datetime.datetime(1970, 1, 1) + datetime.timedelta(seconds=sec)
+    except OverflowError:
+        return "time.Unix(%d, %d)" % (sec, nsec)
+    frac = (".%09d" % nsec).rstrip("0") if nsec else ""
+    return "%04d-%02d-%02d %02d:%02d:%02d%s +0000 UTC" % (t.year, t.month, t.day, t.hour, t.minute, t.second, frac)
+
+
+def _go_capture_info(ci):
+    """fmt's %+v of a gopacket.CaptureInfo whose Timestamp is in UTC."""
+    return "{Timestamp:%s CaptureLength:%d Length:%d InterfaceIndex:%d AncillaryData:[%s]}" % (
+        _go_time(ci.Timestamp), ci.CaptureLength, ci.Length, ci.InterfaceIndex,
+        " ".join(str(a) for a in ci.AncillaryData))
+
+
+def encode_ng_options(o):
+    """NgPacketOptions.toNgOptions (pcapng.go:352-410) as writeOptions writes
+    them (ngwrite.go:118-184): comments, flags, hashes, drop count, packet id,
+    queue, verdicts, then end-of-options; b"" when there is none."""
+    if o is None:
+        return b""
+    out = []
+
+    def put(code, v):
+        out.append(struct.pack("<HH", code, len(v) & 0xFFFF) + v + bytes((4 - (len(v) & 3)) & 3))
+
+    for c in o.Comments:
+        put(1, _b(c))
+    if o.Flags is not None:
+        put(2, struct.pack("<I", o.Flags.ToUint32()))
+    for h in o.Hashes:
+        put(3, bytes([h.Algorithm & 0xFF]) + bytes(h.Hash))
+    if o.DropCount is not None:
+        put(4, struct.pack("<Q", o.DropCount))
+    if o.PacketID is not None:
+        put(5, struct.pack("<Q", o.PacketID))
+    if o.Queue is not None:
+        put(6, struct.pack("<I", o.Queue))
+    for v in o.Verdicts:
+        put(7, bytes([v.Type & 0xFF]) + bytes(v.Data))
+    return b"".join(out) + bytes(4) if out else b""
+
+
+class _WriterBase:
+    """What both writers share: the native writer object (format, interface
+    count, device workspace), the single-packet path on the CPU
+    (gpk_capwrite_batch_host) and the batch path on the device
+    (gpk_capwrite_batch)."""
+
+    def __init__(self, w, fmt):
+        self._w, self._fmt, self._L = w, fmt, _lib.lib()
+        self._h = ctypes.c_void_p()
+        self._cap, self._device = 0, -1
+        _lib.check(self._L.gpk_capwriter_create(ctypes.byref(self._h), fmt, -1, 0))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.gpk_capwriter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _interfaces(self):
+        return self._L.gpk_capwriter_interfaces(self._h)
+
+    def _on_device(self, device, m):
+        """The native writer with a workspace for m output packets on `device`."""
+        if self._device == device and m <= self._cap:
+            return
+        h = ctypes.c_void_p()
+        cap = max(int(m), 2 * self._cap, 1024)
+        _lib.check(self._L.gpk_capwriter_create(ctypes.byref(h), self._fmt, device, cap))
+        if self._fmt == _lib.CAPW_PCAPNG:
+            _lib.check(self._L.gpk_capwriter_set_interfaces(h, self._interfaces()))
+        self._L.gpk_capwriter_destroy(self._h)
+        self._h, self._cap, self._device = h, cap, device
+
+    def _emit(self, fn, *args, size=256, tail=()):
+        """One host-built block: fn(writer, *args, out, cap, *tail) -> length."""
+        while True:
+            buf = ctypes.create_string_buffer(size)
+            n = fn(self._h, *args, buf, size, *tail)
+            if n < 0:
+                return n, b""
+            if n <= size:
+                return n, buf.raw[:n]
+            size = n
+
+    def _error(self, status, ci):
+        if status == _lib.CAPW_ELENGTH:
+            return PcapgoError("invalid capture info %s:  capture length > length" % _go_capture_info(ci))
+        if status == _lib.CAPW_EIFACE:
+            return PcapgoError("Can't send statistics for non existent interface %d; have only %d interfaces"
+                               % (ci.InterfaceIndex, self._interfaces()))
+        if status == _lib.CAPW_EBIG:
+            return PcapgoError("packet block of 4 GiB or more: capture length %d" % ci.CaptureLength)
+        return PcapgoError("packet index out of range")
+
+    @staticmethod
+    def _now(now):
+        if now is None:
+            import time
+            t = time.time_ns()
+            now = (t // 1000000000, t % 1000000000)
+        return _lib.CapwriteOpts(int(now[0]), int(now[1]), 0)
+
+    def _write_one(self, ci, data, options=None, now=None):
+        data = bytes(data)
+        if self._fmt == _lib.CAPW_PCAPNG and not 0 <= ci.InterfaceIndex < self._interfaces():
+            raise self._error(_lib.CAPW_EIFACE, ci)  # ngwrite.go:362: checked before the lengths
+        if ci.CaptureLength != len(data):
+            raise PcapgoError("capture length %d does not match data length %d" % (ci.CaptureLength, len(data)))
+        buf = np.frombuffer(data + bytes(16), np.uint8)
+        off, cap = np.zeros(1, np.uint64), np.array([len(data)], np.uint32)
+        rec = np.zeros(1, _lib.CAPINFO_DTYPE)
+        rec[0] = (int(ci.Timestamp[0]), int(ci.Timestamp[1]), min(max(int(ci.Length), 0), 0xFFFFFFFF),
+                  int(ci.InterfaceIndex), -1)
+        opt = encode_ng_options(options)
+        ob = np.frombuffer(opt, np.uint8) if opt else None
+        oo = np.array([0, len(opt)], np.uint64) if opt else None
+        out = np.empty(len(data) + len(opt) + 64, np.uint8)
+        boff, st, cnt = np.zeros(2, np.uint64), np.zeros(1, np.int32), np.zeros(4, np.uint64)
+        b = _lib.Batch(buf.ctypes.data, off.ctypes.data, cap.ctypes.data, 1, len(data))
+        o = self._now(now)
+        _lib.check(self._L.gpk_capwrite_batch_host(
+            self._h, ctypes.byref(b), None, 1, rec.ctypes.data, ob.ctypes.data if opt else None,
+            oo.ctypes.data if opt else None, ctypes.byref(o), out.ctypes.data, len(out), boff.ctypes.data,
+            st.ctypes.data, cnt.ctypes.data))
+        if st[0] != _lib.CAPW_OK:
+            raise self._error(int(st[0]), ci)
+        self._w.write(out[:int(boff[1])].tobytes())
+
+    def WritePackets(self, data, offsets, caplens, ci, order=None, options=None, skip_errors=False, now=None,
+                     group=0, stream=None):
+        """Write packets order[0..m) (default: all, in batch order) of a device
+        batch: torch device tensors data (uint8), offsets (int64), caplens
+        (int32) as everywhere in this package, ci the packets' CaptureInfo as
+        _lib.CAPINFO_DTYPE (a numpy array, uploaded here, or a uint8 device
+        tensor of it), order an int32 device tensor (BPF.Select's index;
+        repeats allowed). options (NgWriter): one NgPacketOptions or None per
+        OUTPUT packet. The blocks are framed on the device, copied to the host
+        and written to the file object in one write.
+
+        It behaves like a loop of WritePacket calls that returns at the first
+        error: the blocks before it are written, then PcapgoError is raised
+        with the reference's text (the CaptureInfo in it is rendered like Go's
+        %+v for a UTC time; no reference vector pins that rendering).
+        skip_errors=True leaves the packets in error out and writes the rest.
+        now = (sec, nsec): what the pcap formats write for a zero time.Time
+        (the reference calls time.Now() per packet; one instant per call
+        here, the call's own time by default). Returns the blocks written."""
+        import torch
+        dev = offsets.device
+        n = offsets.numel()
+        m = n if order is None else order.numel()
+        if m == 0:
+            return 0
+        if not isinstance(ci, torch.Tensor):
+            ci_host = np.ascontiguousarray(ci, dtype=_lib.CAPINFO_DTYPE)
+            ci = torch.from_numpy(ci_host.view(np.uint8).copy()).to(dev)
+        if ci.numel() != n * _lib.CAPINFO_DTYPE.itemsize:
+            raise ValueError("ci must hold one gpk_capture_info per packet of the batch")
+        opt_d = opt_o = None
+        opt_bytes = 0
+        if options is not None and self._fmt == _lib.CAPW_PCAPNG:
+            if len(options) != m:
+                raise ValueError("options must have one entry per output packet")
+            enc = [encode_ng_options(o) for o in options]
+            opt_bytes = sum(len(e) for e in enc)
+            if opt_bytes:
+                oo = np.zeros(m + 1, np.int64)
+                np.cumsum([len(e) for e in enc], out=oo[1:])
+                opt_o = torch.from_numpy(oo).to(dev)
+                opt_d = torch.from_numpy(np.frombuffer(b"".join(enc) + bytes(16), np.uint8).copy()).to(dev)
+        self._on_device(dev.index or 0, m)
+        if order is None:
+            payload = int(data.numel())
+        else:
+            payload = int(caplens.index_select(0, order.long().clamp(0, max(n - 1, 0))).sum(dtype=torch.int64).item())
+        cap = payload + 36 * m + opt_bytes
+        boff = torch.empty(m + 1, dtype=torch.int64, device=dev)
+        st = torch.empty(m, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(4, dtype=torch.int64, device=dev)
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        o = self._now(now)
+        o.group = int(group)
+        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        for _ in range(2):
+            out = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
+            _lib.check(self._L.gpk_capwrite_batch(
+                self._h, ctypes.byref(b), order.data_ptr() if order is not None else None, m, ci.data_ptr(),
+                opt_d.data_ptr() if opt_d is not None else None, opt_o.data_ptr() if opt_o is not None else None,
+                ctypes.byref(o), out.data_ptr(), cap, boff.data_ptr(), st.data_ptr(), cnt.data_ptr(), sp))
+            counts = cnt.cpu().tolist()
+            if not counts[3]:
+                break
+            cap = counts[1]  # the estimate was short (repeats in `order`): once more with what is needed
+        end, err = counts[1], None
+        if counts[2] and not skip_errors:
+            j = int(torch.nonzero(st != 0)[0].item())
+            end = int(boff[j].item())
+            i = j if order is None else int(order[j].item())
+            code = int(st[j].item())
+            if code == _lib.CAPW_EINDEX:
+                err = self._error(code, None)
+            else:
+                r = ci.view(-1, _lib.CAPINFO_DTYPE.itemsize)[i].cpu().numpy().view(_lib.CAPINFO_DTYPE)[0]
+                err = self._error(code, CaptureInfo((int(r["ts_sec"]), int(r["ts_nsec"])), int(caplens[i].item()),
+                                                    int(r["length"]), int(r["iface"])))
+        if end:
+            self._w.write(out[:end].cpu().numpy().data)
+        if err is not None:
+            raise err
+        return counts[0]
+
+
+class Writer(_WriterBase):
+    """pcapgo.Writer (write.go:25-129)."""
+
+    def __init__(self, w, nanos=False):
+        super().__init__(w, _lib.CAPW_PCAP_NANO if nanos else _lib.CAPW_PCAP_MICRO)
+
+    def WriteFileHeader(self, snaplen, linktype):
+        n, blk = self._emit(self._L.gpk_capwrite_file_header, int(snaplen) & 0xFFFFFFFF, int(linktype) & 0xFFFFFFFF)
+        _lib.check(min(n, 0))
+        self._w.write(blk)
+
+    def WritePacket(self, ci, data, now=None):
+        """now: see WritePackets (a zero Timestamp is written as time.Now())."""
+        self._write_one(ci, data, None, now)
+
+
+class NgWriter(_WriterBase):
+    """pcapgo.NgWriter (ngwrite.go:45-416). There is no bufio layer: every call
+    writes its block to the file object at once, and Flush flushes that object."""
+
+    def __init__(self, w, intf, options):
+        super().__init__(w, _lib.CAPW_PCAPNG)
+        self.options = options
+        si = options.SectionInfo
+        keep = [_b(si.Application), _b(si.Comment), _b(si.Hardware), _b(si.OS)]
+        sec = _lib.CapwSection(*[_lib.CapwBytes(ctypes.cast(ctypes.c_char_p(k), ctypes.c_void_p), len(k))
+                                 for k in keep])
+        n, blk = self._emit(self._L.gpk_capwrite_section_header, ctypes.byref(sec), size=256 + sum(map(len, keep)))
+        _lib.check(min(n, 0))
+        self._w.write(blk)
+        self.AddInterface(intf)
+
+    def AddInterface(self, intf):
+        """Returns the new interface's id."""
+        keep = [_b(intf.Name), _b(intf.Comment), _b(intf.Description), _b(intf.Filter), _b(intf.OS)]
+        f = _lib.CapwInterface(*[_lib.CapwBytes(ctypes.cast(ctypes.c_char_p(k), ctypes.c_void_p), len(k))
+                                 for k in keep], int(intf.TimestampOffset), int(intf.SnapLength) & 0xFFFFFFFF,
+                               int(intf.LinkType) & 0xFFFF, 0)
+        ident = ctypes.c_int(-1)
+        n, blk = self._emit(self._L.gpk_capwrite_add_interface, ctypes.byref(f), size=256 + sum(map(len, keep)),
+                            tail=(ctypes.byref(ident),))
+        _lib.check(min(n, 0))
+        self._w.write(blk)
+        return ident.value
+
+    def WriteInterfaceStats(self, intf, stats):
+        st = _lib.CapwStats(int(stats.LastUpdate[0]), int(stats.StartTime[0]), int(stats.EndTime[0]),
+                            int(stats.LastUpdate[1]), int(stats.StartTime[1]), int(stats.EndTime[1]), 0,
+                            int(stats.PacketsReceived), int(stats.PacketsDropped))
+        n, blk = self._emit(self._L.gpk_capwrite_interface_stats, int(intf), ctypes.byref(st))
+        if n == _lib.CAPW_EIFACE:
+            raise PcapgoError("Can't send statistics for non existent interface %d; have only %d interfaces"
+                              % (intf, self._interfaces()))
+        _lib.check(min(n, 0))
+        self._w.write(blk)
+
+    def WritePacket(self, ci, data):
+        self._write_one(ci, data)
+
+    def WritePacketWithOptions(self, ci, data, opts):
+        self._write_one(ci, data, opts)
+
+    def WriteDecryptionSecretsBlock(self, secretType, secretPayload):
+        p = bytes(secretPayload)
+        n, blk = self._emit(self._L.gpk_capwrite_secrets, int(secretType) & 0xFFFFFFFF,
+                            ctypes.cast(ctypes.c_char_p(p), ctypes.c_void_p), len(p), size=64 + len(p))
+        if n == _lib.CAPW_ESECRETS:
+            raise PcapgoError(ErrUnknownSecretsType)
+        _lib.check(min(n, 0))
+        self._w.write(blk)
+
+    def Flush(self):
+        if hasattr(self._w, "flush"):
+            self._w.flush()
+
+
+def NewWriter(w):
+    return Writer(w)
+
+
+def NewWriterNanos(w):
+    return Writer(w, nanos=True)
+
+
+def NewNgWriterInterface(w, intf, options):
+    return NgWriter(w, intf, options)
+
+
+def NewNgWriter(w, linkType):
+    import dataclasses
+    return NgWriter(w, dataclasses.replace(DefaultNgInterface, LinkType=linkType), DefaultNgWriterOptions)
