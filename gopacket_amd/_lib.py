@@ -107,6 +107,9 @@ EXPORTS = (
     "gpk_capwriter_create", "gpk_capwriter_destroy", "gpk_capwriter_interfaces", "gpk_capwriter_set_interfaces",
     "gpk_capwrite_file_header", "gpk_capwrite_section_header", "gpk_capwrite_add_interface",
     "gpk_capwrite_interface_stats", "gpk_capwrite_secrets", "gpk_capwrite_batch", "gpk_capwrite_batch_host",
+    # include/gpk_serialize.h
+    "gpk_serializer_create", "gpk_serializer_destroy", "gpk_serialize_batch", "gpk_serialize_batch_host",
+    "gpk_serialize_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -195,6 +198,19 @@ class CapwStats(ctypes.Structure):
 class CapwriteOpts(ctypes.Structure):
     """gpk_capwrite_opts"""
     _fields_ = [("now_sec", ctypes.c_int64), ("now_nsec", ctypes.c_uint32), ("group", ctypes.c_uint32)]
+
+
+# include/gpk_serialize.h constants: status[j] is 0, a reference error (> 0) or a scope code (< 0)
+SER_OK = 0
+(SER_ERR_ETH_TYPE_LENGTH, SER_ERR_ETH_LENGTH, SER_ERR_IP6_FIT_LEN, SER_ERR_IP6_JUMBO_MISSING,
+ SER_ERR_IP6_JUMBO_TLV_LEN, SER_ERR_IP6_JUMBO_SMALL, SER_ERR_IP6_JUMBO_TLV_SHORT, SER_ERR_HBH_MULT8,
+ SER_ERR_IP6_FIT, SER_ERR_L4_NO_NETWORK) = range(1, 11)
+SER_ENOLAYER, SER_EHBHLONG, SER_EJUMBOADD, SER_EINDEX, SER_ELAYOUT = -40, -41, -42, -43, -44
+
+
+class SerializeOpts(ctypes.Structure):
+    """gpk_serialize_opts"""
+    _fields_ = [("fix_lengths", ctypes.c_uint32), ("compute_checksums", ctypes.c_uint32), ("group", ctypes.c_uint32)]
 
 
 # include/gpk_afpacket.h constants
@@ -453,6 +469,13 @@ def lib():
         "gpk_capwrite_batch": ([vp, P(Batch), vp, u64, vp, vp, vp, P(CapwriteOpts), vp, u64, vp, vp, vp, vp], c_int),
         "gpk_capwrite_batch_host": ([vp, P(Batch), vp, u64, vp, vp, vp, P(CapwriteOpts), vp, u64, vp, vp, vp],
                                     c_int),
+        "gpk_serializer_create": ([P(vp), c_int, u64], c_int),
+        "gpk_serializer_destroy": ([vp], c_int),
+        "gpk_serialize_batch": ([vp, P(Batch), vp, vp, vp, u64, P(SerializeOpts), vp, u64, vp, vp, vp, vp, vp, vp],
+                                c_int),
+        "gpk_serialize_batch_host": ([vp, P(Batch), vp, vp, vp, u64, P(SerializeOpts), vp, u64, vp, vp, vp, vp, vp],
+                                     c_int),
+        "gpk_serialize_format_error": ([c_int, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

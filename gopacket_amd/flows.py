@@ -21,6 +21,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            tcpassembly's reassembly of a CONNECTION-grouped
                                            batch (assembly.go:536-783, FlushAll :279-290)
   TCPAssembler(ctx, parser, n)             the same over a stream of batches
+  Serializer(max_packets).serialize(...)   gpk_serialize_batch (include/gpk_serialize.h):
+                                           gopacket.SerializeLayers for a decoded batch, from
+                                           its layouts and (edited) fields records
+                                           (writer.go:207-218 and the six layers' SerializeTo)
 """
 import ctypes
 
@@ -507,3 +511,98 @@ class TCPAssembler:
     def close(self):
         self.grouper.close()
         self.assembler.close()
+
+
+class Serializer:
+    """gpk_serialize_batch (include/gpk_serialize.h): gopacket.SerializeLayers for
+    the packets of a decoded device batch, from their layouts and their (edited)
+    gpk_fields records. Owns the handle and its scratch for up to max_packets
+    output packets; device=None makes a host-only serializer (serialize_host)."""
+
+    def __init__(self, max_packets=1, device=0):
+        self.h = ctypes.c_void_p()
+        _lib.check(_lib.lib().gpk_serializer_create(ctypes.byref(self.h), -1 if device is None else int(device),
+                                                    int(max_packets)))
+        self.max_packets = int(max_packets)
+
+    def serialize(self, data, offsets, caplens, layouts, fields, order=None, fix_lengths=False,
+                  compute_checksums=False, out=None, out_cap=None, group=0, stream=None):
+        """Device tensors in: data uint8, offsets int64, caplens int32, layouts
+        and fields the decode's (uint8 views of gpk_layout / gpk_fields), order
+        int32 or None. Returns dict(out, offsets[m+1], caplens[m], status[m],
+        err_args[2m], counts[4]) of device tensors; `out` may be given (uint8,
+        its size is out_cap unless that is given too). A batch that does not fit
+        has counts[3] set. With `out` or `out_cap` given, or without an order,
+        nothing is synchronised here; with an order and neither of them the
+        buffer is sized from the selected packets' lengths, which is one
+        synchronising sum on the device."""
+        import torch
+        n = offsets.numel()
+        m = n if order is None else order.numel()
+        dev = offsets.device
+        if out is None:
+            if out_cap is None:
+                # every packet keeps its bytes at most; headers grow by less than 64 + the Ethernet pad
+                if order is None:
+                    out_cap = int(data.numel()) + 128 * m
+                else:  # a selection: the bytes it names (one synchronising sum)
+                    sel = caplens.index_select(0, order.long().clamp(0, max(n - 1, 0)))
+                    out_cap = int(sel.sum(dtype=torch.int64).item()) + 128 * m
+            out = torch.empty(int(out_cap) + 16, dtype=torch.uint8, device=dev)
+        elif out_cap is None:
+            out_cap = out.numel()
+        res = dict(out=out, offsets=torch.empty(m + 1, dtype=torch.int64, device=dev),
+                   caplens=torch.empty(m, dtype=torch.int32, device=dev),
+                   status=torch.empty(m, dtype=torch.int32, device=dev),
+                   err_args=torch.zeros(2 * m, dtype=torch.int32, device=dev),
+                   counts=torch.zeros(4, dtype=torch.int64, device=dev))
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        o = _lib.SerializeOpts(int(bool(fix_lengths)), int(bool(compute_checksums)), int(group))
+        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        _lib.check(_lib.lib().gpk_serialize_batch(
+            self.h, ctypes.byref(b), layouts.data_ptr(), fields.data_ptr(),
+            order.data_ptr() if order is not None else None, m, ctypes.byref(o), out.data_ptr(), int(out_cap),
+            res["offsets"].data_ptr(), res["caplens"].data_ptr(), res["status"].data_ptr(), res["err_args"].data_ptr(),
+            res["counts"].data_ptr(), sp))
+        return res
+
+    def serialize_host(self, data, offsets, caplens, layouts, fields, order=None, fix_lengths=False,
+                       compute_checksums=False, out_cap=None):
+        """The same over numpy arrays (gpk_serialize_batch_host): data uint8,
+        offsets uint64, caplens uint32, layouts _lib.LAYOUT_DTYPE, fields
+        _lib.FIELDS_DTYPE, order uint32 or None."""
+        import numpy as np
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        caplens = np.ascontiguousarray(caplens, np.uint32)
+        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
+        fields = np.ascontiguousarray(fields, _lib.FIELDS_DTYPE)
+        n = len(caplens)
+        if order is not None:
+            order = np.ascontiguousarray(order, np.uint32)
+        m = n if order is None else len(order)
+        if out_cap is None:
+            idx = np.arange(n) if order is None else order[order < n]
+            out_cap = int(caplens[idx].sum(dtype=np.uint64)) + 2300 * max(m, 1)
+        res = dict(out=np.zeros(int(out_cap), np.uint8), offsets=np.zeros(m + 1, np.uint64),
+                   caplens=np.zeros(m, np.uint32), status=np.zeros(m, np.int32), err_args=np.zeros(2 * m, np.uint32),
+                   counts=np.zeros(4, np.uint64))
+        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
+        o = _lib.SerializeOpts(int(bool(fix_lengths)), int(bool(compute_checksums)), 0)
+        _lib.check(_lib.lib().gpk_serialize_batch_host(
+            self.h, ctypes.byref(b), layouts.ctypes.data, fields.ctypes.data,
+            order.ctypes.data if order is not None else None, m, ctypes.byref(o), res["out"].ctypes.data, int(out_cap),
+            res["offsets"].ctypes.data, res["caplens"].ctypes.data, res["status"].ctypes.data,
+            res["err_args"].ctypes.data, res["counts"].ctypes.data))
+        return res
+
+    def close(self):
+        if self.h:
+            _lib.lib().gpk_serializer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

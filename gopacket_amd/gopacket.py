@@ -10,11 +10,14 @@ Mirrors (reference file:line):
   Payload, Fragment DecodingLayers (base.go:40-124)
   DecodingLayerParser, NewDecodingLayerParser, DecodeLayers, AddDecodingLayer,
   UnsupportedLayerType, DecodingLayerParserOptions (parser.go:182-351)
+  SerializeOptions, SerializeLayers for a decoded batch: SerializeBatch, SerializeError
+  (writer.go:43-52, 207-218; include/gpk_serialize.h)
 
 Decoding always runs on the GPU (through include/gpk.h): DecodeLayers sends
 one packet, DecodeBatch a whole PacketBatch; the per-packet results fill the
 registered layer structs exactly as the reference's DecodeLayers would.
 """
+import ctypes
 import json
 import os
 import struct
@@ -916,3 +919,87 @@ class BatchResult:
             s = s + inst._poff
             e = s + len(inst.LayerPayload())
         return out
+
+
+# ---- serialization: SerializeOptions / SerializeLayers (writer.go:43-218) for a batch
+@dataclass
+class SerializeOptions:
+    """gopacket.SerializeOptions (writer.go:45-52)"""
+    FixLengths: bool = False
+    ComputeChecksums: bool = False
+
+
+class SerializeError(GoError, Exception):
+    """The error SerializeLayers returns for one packet: status > 0 is the
+    reference's error (its text is Error()), status < 0 a scope decision of
+    include/gpk_serialize.h."""
+    SCOPE = {_lib.SER_ENOLAYER: "a layer is present in the fields record but has no slice in the layout "
+                                "(inserting headers is not built)",
+             _lib.SER_EHBHLONG: "the inline HopByHop header is longer than 24 bytes",
+             _lib.SER_EJUMBOADD: "FixLengths would insert a HopByHop header or a jumbo option (addIPv6JumboOption)",
+             _lib.SER_EINDEX: "order names a packet that is not in the batch",
+             _lib.SER_ELAYOUT: "the layout or an option map does not describe this packet"}
+
+    def __init__(self, status, a0=0, a1=0, packet=None):
+        self.status, self.a0, self.a1, self.packet = int(status), int(a0), int(a1), packet
+        Exception.__init__(self, self.Error())
+
+    def Error(self):
+        if self.status < 0:
+            return self.SCOPE.get(self.status, "gpk_serialize status %d" % self.status)
+        if self.status == _lib.SER_ERR_ETH_TYPE_LENGTH:  # %v of an EthernetType is its name
+            from . import layers
+            return "ethernet type %s not compatible with length value %d" % (layers.EthernetTypeString(self.a0), self.a1)
+        buf = ctypes.create_string_buffer(256)
+        _lib.lib().gpk_serialize_format_error(self.status, self.a0, self.a1, buf, len(buf))
+        return buf.value.decode()
+
+    def __str__(self):
+        return self.Error()
+
+    def __repr__(self):
+        return "SerializeError(%d, %d, %d)" % (self.status, self.a0, self.a1)
+
+
+_serializers = {}
+
+
+def SerializeBatch(opts, data, offsets, caplens, layouts, fields, order=None, out=None, raise_errors=False, group=0,
+                   stream=None):
+    """gopacket.SerializeLayers for packets order[0..m) (default: all) of a
+    decoded batch: the layer list include/gpk_serialize.h defines, built from the
+    packets' layouts, the (edited) fields records and the source bytes.
+
+    Device tensors in (torch: data uint8, offsets int64, caplens int32, layouts
+    and fields as the decode wrote them, order int32) give device tensors out;
+    numpy arrays in (uint8, uint64, uint32, LAYOUT_DTYPE, FIELDS_DTYPE, uint32)
+    run on the host and give numpy arrays. Returns dict(out, offsets, caplens,
+    status, err_args, counts): {out, offsets, caplens} is a batch that decodes
+    again. raise_errors=True raises SerializeError for the first packet in
+    error (this synchronises the device path)."""
+    host = isinstance(offsets, np.ndarray)
+    m = len(offsets) if order is None else len(order)
+    key = None if host else (offsets.device.index or 0)
+    s = _serializers.get(key)
+    if s is None or s.max_packets < m:
+        from .flows import Serializer
+        if s is not None:
+            s.close()
+        s = _serializers[key] = Serializer(max(m, 1 << 16), device=key)
+    if host:
+        res = s.serialize_host(data, offsets, caplens, layouts, fields, order, opts.FixLengths, opts.ComputeChecksums,
+                               out_cap=None if out is None else len(out))
+        if out is not None:
+            out[:len(res["out"])] = res["out"]
+            res["out"] = out
+    else:
+        res = s.serialize(data, offsets, caplens, layouts, fields, order, opts.FixLengths, opts.ComputeChecksums,
+                          out=out, group=group, stream=stream)
+    if raise_errors:
+        st = res["status"] if host else res["status"].cpu().numpy()
+        bad = np.nonzero(st)[0]
+        if len(bad):
+            j = int(bad[0])
+            args = res["err_args"] if host else res["err_args"].cpu().numpy().view(np.uint32)
+            raise SerializeError(int(st[j]), int(args[2 * j]), int(args[2 * j + 1]), packet=j)
+    return res
