@@ -101,6 +101,8 @@ EXPORTS = (
     "gpk_bpf_create", "gpk_bpf_destroy", "gpk_bpf_run", "gpk_bpf_select",
     # include/gpk_defrag.h
     "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch",
+    # include/gpk_defrag6.h
+    "gpk_defragger6_create", "gpk_defragger6_destroy", "gpk_defrag6_batch",
     # include/gpk_tcpasm.h
     "gpk_tcpasm_create", "gpk_tcpasm_destroy", "gpk_tcpasm_batch",
     # include/gpk_capwrite.h
@@ -116,7 +118,7 @@ BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<
 BPF_MAX_INSNS = 4096
 
 # include/gpk_flows.h constants
-GROUP_CONNECTION, GROUP_DEFRAG, GROUP_NET_BUCKET = 1, 2, 3
+GROUP_CONNECTION, GROUP_DEFRAG, GROUP_NET_BUCKET, GROUP_DEFRAG6 = 1, 2, 3, 4
 GROUP_NONE, GROUP_USELESS, GROUP_FRAG_TOO_SMALL, GROUP_FRAG_OFFSET, GROUP_FRAG_OVERRUN, GROUP_UNKNOWN = \
     -1, -2, -3, -4, -5, -6
 
@@ -137,6 +139,19 @@ class Datagrams(ctypes.Structure):
                 ("offsets", ctypes.c_void_p), ("caplens", ctypes.c_void_p), ("payload_off", ctypes.c_void_p),
                 ("pending", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("data", ctypes.c_void_p),
                 ("data_cap", ctypes.c_uint64)]
+
+
+# include/gpk_defrag6.h constants
+DEFRAG6_HELD, DEFRAG6_CARRIED = -32, -33
+DEFRAG6_MAX_LIST = 8192
+
+
+class Datagrams6(ctypes.Structure):
+    """gpk_datagrams6: the outputs of gpk_defrag6_batch (device arrays)."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("last", ctypes.c_void_p), ("head", ctypes.c_void_p),
+                ("length", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("caplens", ctypes.c_void_p),
+                ("payload_off", ctypes.c_void_p), ("pending", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("data", ctypes.c_void_p), ("data_cap", ctypes.c_uint64)]
 
 
 # include/gpk_tcpasm.h constants
@@ -454,6 +469,9 @@ def lib():
         "gpk_defragger_create": ([P(vp), c_int, u64], c_int),
         "gpk_defragger_destroy": ([vp], c_int),
         "gpk_defrag_batch": ([vp, P(Batch), P(Results), P(Groups), P(Datagrams), vp], c_int),
+        "gpk_defragger6_create": ([P(vp), c_int, u64], c_int),
+        "gpk_defragger6_destroy": ([vp], c_int),
+        "gpk_defrag6_batch": ([vp, P(Batch), P(Results), P(Groups), u64, P(Datagrams6), vp], c_int),
         "gpk_tcpasm_create": ([P(vp), c_int, u64], c_int),
         "gpk_tcpasm_destroy": ([vp], c_int),
         "gpk_tcpasm_batch": ([vp, P(Batch), P(Results), P(Groups), P(TcpasmOpts), P(TcpStreams), vp], c_int),

@@ -5,7 +5,8 @@
 //   1. key_kernel     one lane per packet: derive the consumer's key from the
 //                     decode results (records, layouts) and the packet bytes,
 //                     exactly as the consumer would build it (a [2]Flow, an
-//                     ipv4{Flow, Id}, or a FastHash bucket), or the reason the
+//                     ipv4{Flow, Id}, an IPv6 Fragment header's Identification,
+//                     or a FastHash bucket), or the reason the
 //                     packet has no key; store the key words and a 64-bit hash
 //   2. insert_kernel  open-addressing table in HBM: the hash picks the slot,
 //                     the full key words decide equality (a hash collision
@@ -27,6 +28,7 @@
 
 #include "../../include/gpk_flows.h"
 #include "gpk_devguard.h"
+#include "gpk_frag6.h"
 
 // gpk_host.cpp: gpk_decode_batch with the fused key derivation (library-internal)
 extern "C" int gpk_decode_batch_keys(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results* o, int key_kind,
@@ -164,6 +166,33 @@ __global__ void __launch_bounds__(256) key_kernel(KeyArgs a) {
     a.hash[i] = b;
     return;
   }
+  uint64_t h = 0x9E3779B97F4A7C15ull;
+  for (int k = 0; k < kKeyWords; k++) {
+    a.keys[i * kKeyWords + k] = w[k];
+    h = (h ^ w[k]) * 0xBF58476D1CE4E5B9ull;
+    h ^= h >> 29;
+  }
+  a.hash[i] = mix64(h);
+}
+
+// GPK_GROUP_DEFRAG6, a kernel of its own so that the other kinds' kernel stays
+// as it is: ip6defrag's container[fg.Identification] (defrag.go:98), for the
+// packets whose IPv6 payload leads to a Fragment header (gpk_frag6.h)
+__global__ void __launch_bounds__(256) key6_kernel(KeyArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n) return;
+  const gpk_layout& L = a.layouts[i];
+  const uint8_t* p = a.data + a.offsets[i];
+  const uint32_t s6 = L.start[kSlotIp6];
+  gpk::Frag6 f;
+  if (s6 == GPK_LAYOUT_ABSENT || !gpk::find_frag6(p + s6, L.end[kSlotIp6] - s6, &f)) {
+    a.code[i] = GPK_GROUP_NONE;
+    return;
+  }
+  a.code[i] = 0;
+  const uint8_t* fh = p + s6 + f.hdr;
+  uint32_t w[kKeyWords] = {4u, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  w[9] = (uint32_t)fh[4] << 24 | (uint32_t)fh[5] << 16 | (uint32_t)fh[6] << 8 | fh[7];  // ip6.go:659
   uint64_t h = 0x9E3779B97F4A7C15ull;
   for (int k = 0; k < kKeyWords; k++) {
     a.keys[i * kKeyWords + k] = w[k];
@@ -405,7 +434,9 @@ extern "C" int gpk_group_batch(gpk_grouper* g, const gpk_batch* b, const gpk_res
                                const gpk_groups* o, void* stream) {
   if (!g || !b || !r || !o || !r->records || !o->group_of || !o->perm || !o->start || !o->first || !o->counts)
     return GPK_EINVAL;
-  if (kind != GPK_GROUP_CONNECTION && kind != GPK_GROUP_DEFRAG && kind != GPK_GROUP_NET_BUCKET) return GPK_EINVAL;
+  if (kind != GPK_GROUP_CONNECTION && kind != GPK_GROUP_DEFRAG && kind != GPK_GROUP_NET_BUCKET &&
+      kind != GPK_GROUP_DEFRAG6)
+    return GPK_EINVAL;
   if (kind == GPK_GROUP_NET_BUCKET && (!r->flows || buckets == 0 || buckets > (1u << 16) || (buckets & (buckets - 1))))
     return GPK_EINVAL;
   if (kind != GPK_GROUP_NET_BUCKET && (!r->layouts || !b->data || !b->offsets)) return GPK_EINVAL;
@@ -425,7 +456,10 @@ extern "C" int gpk_group_batch(gpk_grouper* g, const gpk_batch* b, const gpk_res
   }
   KeyArgs a{b->data, b->offsets, b->caplens, r->records, r->layouts, r->flows, n, kind, buckets,
             g->keys, g->hash, g->code, g->bucket_min};
-  hipLaunchKernelGGL(key_kernel, grd, blk, 0, s, a);
+  if (kind == GPK_GROUP_DEFRAG6)
+    hipLaunchKernelGGL(key6_kernel, grd, blk, 0, s, a);
+  else
+    hipLaunchKernelGGL(key_kernel, grd, blk, 0, s, a);
   g->buckets = buckets;
   return group_rest(g, n, kind, *o, s);
 }

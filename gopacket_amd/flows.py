@@ -9,6 +9,8 @@ with a Go map, for a whole batch in HBM.
                                            (ip4defrag/defrag.go:85-105,328-341)
   kind NET_BUCKET                          int(NetworkFlow().FastHash()) & (buckets-1)
                                            (doc.go:219-225)
+  kind DEFRAG6                             ip6defrag container[fg.Identification]
+                                           (ip6defrag/defrag.go:98)
 
 Groups come in order of first appearance; packets inside a group in batch
 order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
@@ -17,6 +19,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            ip4defrag's reassembly of a DEFRAG-grouped
                                            batch (defrag.go:113-132,214-326)
   IPv4Defragmenter(ctx, parser, n)         the same over a stream of batches
+  Defragmenter6(max_packets).defrag(...)   gpk_defrag6_batch (include/gpk_defrag6.h):
+                                           ip6defrag's reassembly of a DEFRAG6-grouped
+                                           batch (ip6defrag/defrag.go:82-178)
+  IPv6Defragmenter(ctx, parser, n)         the same over a stream of batches
   Assembler(max_packets).assemble(...)     gpk_tcpasm_batch (include/gpk_tcpasm.h):
                                            tcpassembly's reassembly of a CONNECTION-grouped
                                            batch (assembly.go:536-783, FlushAll :279-290)
@@ -30,7 +36,8 @@ import ctypes
 
 from . import _lib
 
-CONNECTION, DEFRAG, NET_BUCKET = _lib.GROUP_CONNECTION, _lib.GROUP_DEFRAG, _lib.GROUP_NET_BUCKET
+CONNECTION, DEFRAG, NET_BUCKET, DEFRAG6 = (_lib.GROUP_CONNECTION, _lib.GROUP_DEFRAG, _lib.GROUP_NET_BUCKET,
+                                           _lib.GROUP_DEFRAG6)
 NONE, USELESS, FRAG_TOO_SMALL, FRAG_OFFSET, FRAG_OVERRUN, UNKNOWN = (
     _lib.GROUP_NONE, _lib.GROUP_USELESS, _lib.GROUP_FRAG_TOO_SMALL, _lib.GROUP_FRAG_OFFSET,
     _lib.GROUP_FRAG_OVERRUN, _lib.GROUP_UNKNOWN)
@@ -262,6 +269,172 @@ class IPv4Defragmenter:
         out.update(verdict=v, last=out["last"][:D] - P, length=out["length"][:D], offsets=out["offsets"][:D],
                    caplens=out["caplens"][:D], payload_off=out["payload_off"][:D], pending=pend - P,
                    counts=counts, datagrams=D)
+        return out
+
+    def close(self):
+        self.grouper.close()
+        self.defragmenter.close()
+
+
+HELD6, CARRIED6 = _lib.DEFRAG6_HELD, _lib.DEFRAG6_CARRIED
+
+
+class Defragmenter6:
+    """gpk_defrag6_batch (include/gpk_defrag6.h): the IPv6 layers
+    ip6defrag.DefragIPv6 would have returned for a decoded, DEFRAG6-grouped
+    batch, every packet's verdict and the fragments it holds. One call behaves
+    like a fresh NewIPv6Defragmenter() fed the batch in order. A key is never
+    flushed (a completed datagram comes again with every later call on its
+    key); no time (DiscardOlderThan)."""
+
+    def __init__(self, max_packets, device=0):
+        self.h = ctypes.c_void_p()
+        _lib.check(_lib.lib().gpk_defragger6_create(ctypes.byref(self.h), device, int(max_packets)))
+        self.max_packets = int(max_packets)
+
+    def defrag(self, data, offsets, caplens, records, layouts, groups, carry=0, data_cap=None, out_data=None,
+               stream=None):
+        """Device tensors in: the batch, its records and layouts, and `groups`
+        (Grouper.group(kind=DEFRAG6) of it). The calls of the first `carry`
+        packets build state only (verdict CARRIED6, nothing emitted). Returns a
+        dict of device tensors: verdict[n], last/head/length/offsets/caplens/
+        payload_off (n entries, counts[0] used), pending (counts[1] used),
+        counts[4] (datagrams, pending, bytes needed, overflow) and data.
+        data_cap defaults to the batch's data size, which does NOT always
+        suffice here: every later call on a completed key returns its datagram
+        again. On overflow (counts[3]) the datagrams that fit are whole and
+        counts[2] is the capacity a second call needs. {data, offsets[:D],
+        caplens[:D]} is a batch the parsers decode; length[j] is the payload's
+        byte count (the reference's own Length field stays 0)."""
+        import torch
+        n = offsets.numel()
+        dev = offsets.device
+        if out_data is None:
+            cap = int(data.numel() if data_cap is None else data_cap)
+            out_data = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
+        else:
+            cap = int(out_data.numel() if data_cap is None else data_cap)
+        m = max(n, 1)
+        i32 = torch.int32
+        out = dict(verdict=torch.empty(m, dtype=i32, device=dev), last=torch.empty(m, dtype=i32, device=dev),
+                   head=torch.empty(m, dtype=i32, device=dev), length=torch.empty(m, dtype=i32, device=dev),
+                   offsets=torch.empty(m, dtype=torch.int64, device=dev),
+                   caplens=torch.empty(m, dtype=i32, device=dev), payload_off=torch.empty(m, dtype=i32, device=dev),
+                   pending=torch.empty(m, dtype=i32, device=dev),
+                   counts=torch.zeros(4, dtype=torch.int64, device=dev), data=out_data)
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        g = _lib.Groups(groups["group_of"].data_ptr(), groups["perm"].data_ptr(), groups["start"].data_ptr(),
+                        groups["first"].data_ptr(), groups["counts"].data_ptr())
+        d = _lib.Datagrams6(*[out[k].data_ptr() for k in ("verdict", "last", "head", "length", "offsets", "caplens",
+                                                          "payload_off", "pending", "counts")],
+                            out_data.data_ptr(), cap)
+        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        _lib.check(_lib.lib().gpk_defrag6_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g), int(carry),
+                                                ctypes.byref(d), sp))
+        out["verdict"] = out["verdict"][:n]
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().gpk_defragger6_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class IPv6Defragmenter:
+    """A streaming ip6defrag.IPv6Defragmenter over device batches: the listed
+    fragments stay on the device (pack_batch of `pending`) and go in front of
+    the next batch as its `carry` packets, which reproduces the reference's
+    lists exactly (first arrivals stay first, nothing was ever removed) without
+    returning their datagrams a second time. Each call decodes (with layouts),
+    groups and reassembles carried + new packets; `verdict`, `last` and `head`
+    are mapped back to the caller's indices. head[j] < 0 says the header came
+    from a carried packet of an earlier batch (-1 is the last of them); its
+    bytes are in the datagram all the same.
+
+    The reference never removes a key (only DiscardOlderThan does, and time is
+    out of scope), so by default the state grows without bound, as the
+    reference's does: flush() is the caller's DiscardOlderThan. Scope decision
+    that departs from the reference: with drop_completed=True a key that
+    returned a datagram in a call is not carried into the next one, so it does
+    not return that datagram again in later batches and its state is freed."""
+
+    def __init__(self, ctx, parser, max_packets, device=0, drop_completed=False):
+        self.ctx, self.parser = ctx, parser
+        self.max_packets = int(max_packets)
+        self.drop_completed = bool(drop_completed)
+        self.grouper = Grouper(self.max_packets, device)
+        self.defragmenter = Defragmenter6(self.max_packets, device)
+        self._pending = None  # (data, offsets, caplens) on the device
+
+    @property
+    def pending_count(self):
+        return 0 if self._pending is None else int(self._pending[1].numel())
+
+    def flush(self):
+        """Forget every held fragment; returns how many there were."""
+        k = self.pending_count
+        self._pending = None
+        return k
+
+    def defrag(self, data, offsets, caplens):
+        """One batch of packets (device tensors: uint8 data, int64 offsets,
+        int32 caplens). Returns Defragmenter6.defrag's dict for the caller's
+        packets, with `verdict`, `last` and `head` in the caller's indices and
+        counts/pending on the host: datagrams, data, offsets, caplens, ..."""
+        import torch
+        dev = offsets.device
+        P = self.pending_count
+        if P:
+            pd, po, pc = self._pending
+            base = pd.numel()
+            data = torch.cat([pd, data])
+            offsets = torch.cat([po, offsets + base])
+            caplens = torch.cat([pc, caplens])
+        n = offsets.numel()
+        if n > self.max_packets:
+            raise ValueError("pending + batch exceed max_packets")
+        if n == 0:
+            e32, e64 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
+            return dict(verdict=e32, last=e32, head=e32, length=e32, offsets=e64, caplens=e32, payload_off=e32,
+                        pending=e32, counts=[0, 0, 0, 0], datagrams=0,
+                        data=torch.empty(0, dtype=torch.uint8, device=dev))
+        rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+        lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+        flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
+        st = torch.cuda.current_stream()
+        self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
+        groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=DEFRAG6, stream=st)
+        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, stream=st)
+        counts = out["counts"].cpu().tolist()
+        if counts[3]:  # re-emission: the batch's size does not bound the datagrams' bytes
+            out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, data_cap=counts[2],
+                                           stream=st)
+            counts = out["counts"].cpu().tolist()
+        D, K = counts[0], counts[1]
+        pend = out["pending"][:K]
+        if K and D and self.drop_completed:
+            gof = groups["group_of"].long()
+            done = torch.zeros(n, dtype=torch.bool, device=dev)
+            done[gof.index_select(0, out["last"][:D].long())] = True
+            pend = pend[~done.index_select(0, gof.index_select(0, pend.long()))]
+            K = int(pend.numel())
+        if K:
+            total = int(caplens.index_select(0, pend.long()).sum(dtype=torch.int64).item())
+            d2, o2, c2 = pack_batch(data, offsets, caplens, pend.contiguous(), total_bytes=total, stream=st)
+            self._pending = (d2[:total], o2, c2)
+        else:
+            self._pending = None
+        counts[1] = K
+        out.update(verdict=out["verdict"][P:], last=out["last"][:D] - P, head=out["head"][:D] - P,
+                   length=out["length"][:D], offsets=out["offsets"][:D], caplens=out["caplens"][:D],
+                   payload_off=out["payload_off"][:D], pending=pend - P, counts=counts, datagrams=D)
         return out
 
     def close(self):

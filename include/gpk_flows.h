@@ -15,6 +15,10 @@
  *                          (ip4defrag/defrag.go:328-341), for the packets
  *                          DefragIPv4WithTimestamp looks up (:85-105: dontDefrag
  *                          :160-170, securityChecks :173-196)
+ *   GPK_GROUP_DEFRAG6      ip6defrag: container[fg.Identification], the 32-bit
+ *                          Identification alone (ip6defrag/defrag.go:98), for the
+ *                          packets that carry an IPv6 Fragment header; which header
+ *                          that is, is fixed in gpk_defrag6.h
  *   GPK_GROUP_NET_BUCKET   the sharding idiom of doc.go:219-225:
  *                          int(net.NetworkFlow().FastHash()) & (buckets-1)
  *
@@ -45,10 +49,11 @@ extern "C" {
 #define GPK_GROUP_CONNECTION 1
 #define GPK_GROUP_DEFRAG 2
 #define GPK_GROUP_NET_BUCKET 3
+#define GPK_GROUP_DEFRAG6 4
 
 /* group_of[i] for a packet in no group */
 #define GPK_GROUP_NONE (-1)           /* the key does not apply: no TCP / no network layer /
-                                         not a fragment (dontDefrag)                      */
+                                         not a fragment (dontDefrag; no IPv6 Fragment header) */
 #define GPK_GROUP_USELESS (-2)        /* tcpassembly ignores it: no SYN/FIN/RST, no payload */
 #define GPK_GROUP_FRAG_TOO_SMALL (-3) /* securityChecks: "fragment too small"  defrag.go:177 */
 #define GPK_GROUP_FRAG_OFFSET (-4)    /* securityChecks: "fragment offset too big"     :183 */
@@ -76,8 +81,8 @@ typedef struct gpk_groups {
 
 /* Group the packets of a decoded batch (device-resident, as for
  * gpk_decode_batch) by `kind`. res must hold records and layouts (CONNECTION,
- * DEFRAG; decoded with layouts) or records and flows (NET_BUCKET, decoded
- * with GPK_OUT_FLOWS); buckets is a power of two (NET_BUCKET only).
+ * DEFRAG, DEFRAG6; decoded with layouts) or records and flows (NET_BUCKET,
+ * decoded with GPK_OUT_FLOWS); buckets is a power of two (NET_BUCKET only).
  * Asynchronous on `stream`. */
 int gpk_group_batch(gpk_grouper* g, const gpk_batch* batch, const gpk_results* res, int kind, uint32_t buckets,
                     const gpk_groups* out, void* stream);
