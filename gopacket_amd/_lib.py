@@ -112,6 +112,9 @@ EXPORTS = (
     # include/gpk_serialize.h
     "gpk_serializer_create", "gpk_serializer_destroy", "gpk_serialize_batch", "gpk_serialize_batch_host",
     "gpk_serialize_format_error",
+    # include/gpk_tunnel.h
+    "gpk_tunneler_create", "gpk_tunneler_destroy", "gpk_tunnel_batch", "gpk_tunnel_batch_host",
+    "gpk_tunneler_set_sum_threshold", "gpk_tunnel_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -226,6 +229,36 @@ SER_ENOLAYER, SER_EHBHLONG, SER_EJUMBOADD, SER_EINDEX, SER_ELAYOUT = -40, -41, -
 class SerializeOpts(ctypes.Structure):
     """gpk_serialize_opts"""
     _fields_ = [("fix_lengths", ctypes.c_uint32), ("compute_checksums", ctypes.c_uint32), ("group", ctypes.c_uint32)]
+
+
+# include/gpk_tunnel.h constants
+LT_GRE, LT_VXLAN, LT_GENEVE = 18, 116, 120
+TUN_GRE, TUN_VXLAN, TUN_GENEVE, TUN_ALL = 1, 2, 4, 7
+TUN_GRE_CSUM = 1
+TUN_NONE, TUN_UNKNOWN = -1, -2
+(TUN_CLASS_ETHERNET, TUN_CLASS_DOT1Q, TUN_CLASS_IPV4, TUN_CLASS_IPV6, TUN_CLASS_NOINNER,
+ TUN_CLASS_FAILED) = range(6)
+TUN_NCLASS = 6
+(TUN_ERR_VXLAN_SMALL, TUN_ERR_GRE_SMALL, TUN_ERR_GRE_TRUNCATED, TUN_ERR_GENEVE_OPT_SHORT, TUN_ERR_GENEVE_OPT_LEN,
+ TUN_ERR_GENEVE_SHORT, TUN_ERR_GENEVE_OPTS_SHORT) = range(70, 77)
+TUN_ST_TRUNCATED, TUN_ST_CSUM, TUN_ST_VALID = 1, 2, 4
+TUN_VX_I, TUN_VX_G, TUN_VX_D, TUN_VX_A = 1, 2, 4, 8
+TUN_GN_O, TUN_GN_C = 1, 2
+TUN_SUM_GROUP_BYTES = 8192
+# gpk_tunnel (72 B): one decoded tunnel header
+TUNNEL_DTYPE = np.dtype([
+    ("kind", "u1"), ("err", "u1"), ("status", "u1"), ("bits", "u1"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("hdr_off", "<u4"), ("contents_len", "<u4"), ("inner_off", "<u4"), ("inner_len", "<u4"), ("next_type", "<i4"),
+    ("vni", "<u4"), ("protocol", "<u2"), ("gbp_id", "<u2"), ("raw0", "u1"), ("raw1", "u1"), ("gre_checksum", "<u2"),
+    ("gre_offset", "<u2"), ("gre_correct", "<u2"), ("gre_key", "<u4"), ("gre_seq", "<u4"), ("gre_ack", "<u4"),
+    ("count", "<u4"), ("list_off", "<u4"), ("gn_version", "u1"), ("gn_options_length", "u1"), ("reserved", "<u2")])
+
+
+class Tunnels(ctypes.Structure):
+    """gpk_tunnels: the outputs of gpk_tunnel_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("in_offsets", ctypes.c_void_p), ("in_caplens", ctypes.c_void_p), ("tunnels", ctypes.c_void_p),
+                ("counts", ctypes.c_void_p)]
 
 
 # include/gpk_afpacket.h constants
@@ -494,6 +527,12 @@ def lib():
         "gpk_serialize_batch_host": ([vp, P(Batch), vp, vp, vp, u64, P(SerializeOpts), vp, u64, vp, vp, vp, vp, vp],
                                      c_int),
         "gpk_serialize_format_error": ([c_int, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_tunneler_create": ([P(vp), c_int, u64], c_int),
+        "gpk_tunneler_destroy": ([vp], c_int),
+        "gpk_tunnel_batch": ([vp, vp, vp, P(Batch), P(Results), u32, u32, P(Tunnels), vp], c_int),
+        "gpk_tunnel_batch_host": ([vp, P(Batch), P(Results), u32, u32, P(Tunnels)], c_int),
+        "gpk_tunneler_set_sum_threshold": ([vp, u32], c_int),
+        "gpk_tunnel_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

@@ -686,6 +686,19 @@ static int with_tables(gpk_ctx* c, const gpk_parser* p, gpk::KParams& P, hipStre
   if (rc || !mark) return rc;
   return note_launch(c, slot, s);
 }
+// ... for the library's other pipelines that read the parser's tables
+// (gpk_tunnel.hip): the host tables, and `step` enqueued on stream with their
+// device copy, which stays valid until the step's work completes
+extern "C" __attribute__((visibility("hidden"))) const gpk::DevTables* gpk_parser_tables(const gpk_parser* p) {
+  return &p->tab;
+}
+extern "C" __attribute__((visibility("hidden"))) int gpk_with_device_tables(
+    gpk_ctx* c, const gpk_parser* p, void* stream, int (*step)(const gpk::DevTables*, void*), void* arg) {
+  if (!c || !p || !step) return GPK_EINVAL;
+  gpk::KParams P{};
+  P.first = p->first;
+  return with_tables(c, p, P, (hipStream_t)stream, true, [&]() -> int { return step(P.tab, arg); });
+}
 // ... for the plain decode launch
 static int launch_decode(gpk_ctx* c, const gpk_parser* p, gpk::KParams& P, bool layouts, hipStream_t s) {
   return with_tables(c, p, P, s, true, [&]() -> int {

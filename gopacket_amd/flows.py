@@ -31,6 +31,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            gopacket.SerializeLayers for a decoded batch, from
                                            its layouts and (edited) fields records
                                            (writer.go:207-218 and the six layers' SerializeTo)
+  Detunneler(max_packets).peel(...)        gpk_tunnel_batch (include/gpk_tunnel.h): the GRE,
+                                           VXLAN and Geneve headers of the packets whose decode
+                                           stopped at one (layers/gre.go, vxlan.go, geneve.go),
+                                           and their inner packets as zero-copy batches
 """
 import ctypes
 
@@ -772,6 +776,89 @@ class Serializer:
     def close(self):
         if self.h:
             _lib.lib().gpk_serializer_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Detunneler:
+    """gpk_tunnel_batch (include/gpk_tunnel.h): one tunnel level peeled off a
+    decoded device batch. Owns the workspace of the scans for up to max_packets
+    packets; device=None makes a host-only one (peel_host)."""
+
+    KEYS = ("verdict", "class_start", "index", "in_offsets", "in_caplens", "tunnels", "counts")
+
+    def __init__(self, max_packets=1, device=0):
+        self.h = ctypes.c_void_p()
+        if device is not None:
+            _lib.check(_lib.lib().gpk_tunneler_create(ctypes.byref(self.h), int(device), int(max_packets)))
+        self.max_packets = int(max_packets)
+
+    def set_sum_threshold(self, nbytes):
+        """Lane group of the GRE sum: 64 lanes from `nbytes` on, 16 below."""
+        _lib.check(_lib.lib().gpk_tunneler_set_sum_threshold(self.h, int(nbytes)))
+
+    def peel(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True,
+             out=None, stream=None):
+        """Device tensors in: the batch, and the records and layouts of
+        ctx.decode_device(parser, ...) for it. Returns dict(verdict[n],
+        class_start[7], index[n], in_offsets[n], in_caplens[n], tunnels[72 n]
+        (uint8, _lib.TUNNEL_DTYPE), counts[8]) of device tensors (or fills
+        `out`); entries at and past counts[0] are not written. Class c's inner
+        batch is (data, in_offsets[class_start[c]:class_start[c+1]],
+        in_caplens[...]) for a parser whose first layer is the class's type."""
+        import torch
+        n = offsets.numel()
+        dev = offsets.device
+        if out is None:
+            out = dict(verdict=torch.empty(n, dtype=torch.int32, device=dev),
+                       class_start=torch.zeros(7, dtype=torch.int32, device=dev),
+                       index=torch.empty(n, dtype=torch.int32, device=dev),
+                       in_offsets=torch.empty(n, dtype=torch.int64, device=dev),
+                       in_caplens=torch.empty(n, dtype=torch.int32, device=dev),
+                       tunnels=torch.empty(n * _lib.TUNNEL_DTYPE.itemsize, dtype=torch.uint8, device=dev),
+                       counts=torch.zeros(8, dtype=torch.int32, device=dev))
+        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = _lib.Tunnels(*[out[k].data_ptr() for k in self.KEYS])
+        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        _lib.check(_lib.lib().gpk_tunnel_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                               _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o), sp))
+        return out
+
+    @staticmethod
+    def peel_host(data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_tunnel_batch_host); `fill` is the byte the outputs start with."""
+        import numpy as np
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        caplens = np.ascontiguousarray(caplens, np.uint32)
+        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
+        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
+        n = len(caplens)
+
+        def arr(count, dt):
+            a = np.empty(count, dt)
+            a.view(np.uint8)[:] = fill
+            return a
+        out = dict(verdict=arr(n, np.int32), class_start=arr(7, np.uint32), index=arr(n, np.uint32),
+                   in_offsets=arr(n, np.uint64), in_caplens=arr(n, np.uint32), tunnels=arr(n, _lib.TUNNEL_DTYPE),
+                   counts=arr(8, np.uint32))
+        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
+        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
+        o = _lib.Tunnels(*[out[k].ctypes.data for k in Detunneler.KEYS])
+        _lib.check(_lib.lib().gpk_tunnel_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                                    _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o)))
+        return out
+
+    def close(self):
+        if self.h:
+            _lib.lib().gpk_tunneler_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -607,6 +607,7 @@ class DecodingLayerParser:
         self.Truncated = False
         self._ctx = ctx
         self._overrides = None  # next-layer table entries of this parser alone (DecodeFromBytes)
+        self._host_decoder = None  # f(parser, data, offsets, caplens) -> results, instead of the device (tests)
         dlc = DecodingLayerMap()  # NewDecodingLayerParser's default container (parser.go:226)
         for d in decoders:
             dlc = dlc.Put(d)
@@ -615,7 +616,10 @@ class DecodingLayerParser:
     def SetDecodingLayerContainer(self, dlc):
         """parser.go:238-241: replaces every registered decoder."""
         self._dlc = dlc
-        self._decoders = dlc._instances()  # kind -> instance
+        inst = dlc._instances()
+        self._decoders = {k: d for k, d in inst.items() if not getattr(d, "tunnel_kind", 0)}  # kind -> instance
+        # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
+        self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
         self._cfg = None
 
     def AddDecodingLayer(self, d):
@@ -655,16 +659,27 @@ class DecodingLayerParser:
         """Decode one packet on the GPU; fills the registered layers and the
         `decoded` list (truncated first, as parser.go:303-317 does)."""
         batch = PacketBatch.from_packets([data])
+        if self._tunnels:  # one packet: the host entry peels (gpk_tunnel_batch_host)
+            return TunnelBatchResult(self, batch, _lib.OUT_ALL, True, device=False).Hydrate(0, decoded)
         res = self.DecodeBatch(batch, layouts=True)
         return res.Hydrate(0, decoded)
 
-    def DecodeBatch(self, batch, layouts=False, outputs=_lib.OUT_ALL, fields=False):
+    def DecodeBatch(self, batch, layouts=False, outputs=_lib.OUT_ALL, fields=False, gre_checksum=True):
         """DecodeLayers for every packet of the batch on the device. fields=True
         also returns each packet's scalar layer fields and IPv4/TCP option maps
         computed on the device (BatchResult.fields, FIELDS_DTYPE;
         BatchResult.IPv4Options / TCPOptions): in the decode launch itself
         (gpk_decode_batch_fields) when layouts=False, else from the layouts
-        (gpk_extract_fields), which Hydrate needs."""
+        (gpk_extract_fields), which Hydrate needs.
+
+        A parser that holds layers.GRE, VXLAN or Geneve returns a
+        TunnelBatchResult instead: the outer decode, then up to
+        MAX_TUNNEL_LEVELS times a peel (gpk_tunnel_batch) and the decode of
+        each inner class, all on the device (layouts are always kept)."""
+        if self._tunnels:
+            if fields:
+                raise ValueError("fields=True is not available for a parser with tunnel layers")
+            return TunnelBatchResult(self, batch, outputs, gre_checksum)
         cfg = self._config(outputs)
         if fields:
             r, f = self.ctx().decode_host_fields(cfg, batch.data, batch.offsets, batch.caplens, layouts=layouts)
@@ -919,6 +934,218 @@ class BatchResult:
             s = s + inst._poff
             e = s + len(inst.LayerPayload())
         return out
+
+
+# ---- tunnels: DecodeLayers with layers.GRE / VXLAN / Geneve in the parser ---------
+MAX_TUNNEL_LEVELS = 8  # peels per batch; a scope decision, not a limit of the reference
+_TUN_CLASS_TYPES = (17, 15, 20, 21)  # GPK_TUN_CLASS_ETHERNET .. _IPV6: the inner parser's first layer
+_TUN_LAYER_TYPE = {_lib.TUN_GRE: _lib.LT_GRE, _lib.TUN_VXLAN: _lib.LT_VXLAN, _lib.TUN_GENEVE: _lib.LT_GENEVE}
+
+
+class TunnelLevelsExceeded(RuntimeError):
+    """A batch still has tunnel candidates after MAX_TUNNEL_LEVELS peels."""
+
+
+class TunnelPart:
+    """One decode of one tunnel level: the packets of the level whose slices
+    start at LayerType `first`. index: the level-0 packet of each; batch: the
+    slices as a PacketBatch over the level-0 data (no byte is moved); result:
+    the BatchResult of this slice batch (records, err_args, flows, layouts),
+    i.e. the level's own checksum and flow outputs; peel: gpk_tunnel_batch's
+    outputs for it (host arrays), the tunnel headers found at its end."""
+
+    def __init__(self, first, index, batch, result, peel):
+        self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
+
+
+class TunnelBatchResult:
+    """DecodeBatch of a parser with tunnel layers: per packet the composed
+    decoded list (outer + [tunnel] + inner, repeated), the composed error and
+    Truncated (the OR of every level's and every tunnel header's), and
+    Level(k): the TunnelParts of level k, whose batches go to a Grouper,
+    Assembler, BPF or WritePackets as any batch does."""
+
+    def __init__(self, parser, batch, outputs=_lib.OUT_ALL, gre_checksum=True, device=True):
+        self.parser, self.batch = parser, batch
+        self.levels = []
+        self._chain = [[] for _ in range(len(batch))]
+        kinds = 0
+        for k in parser._tunnels:
+            kinds |= k
+        run = self._run_device if device else self._run_host
+        run(outputs, kinds, gre_checksum)
+
+    def _clone(self, first):
+        import copy
+        p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
+        p.first, p._tunnels, p._cfg = LayerType(first), {}, None
+        return p
+
+    def _add_part(self, level, first, index, offsets, caplens, r, peel):
+        if len(self.levels) <= level:
+            self.levels.append([])
+        p = self._clone(first)
+        part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
+                          BatchResult(p, None, r), peel)
+        part.result.batch = part.batch
+        self.levels[level].append(part)
+        for pos, g in enumerate(index):
+            self._chain[int(g)].append((part, pos))
+        return part
+
+    def _next_work(self, part, level):
+        """The inner batches of a part: (first type, positions in the compact list)."""
+        pl = part.peel
+        m, cs = int(pl["counts"][0]), [int(x) for x in pl["class_start"]]
+        if m and level >= MAX_TUNNEL_LEVELS:
+            raise TunnelLevelsExceeded("packets still end at a tunnel header after %d levels (MAX_TUNNEL_LEVELS)"
+                                       % MAX_TUNNEL_LEVELS)
+        work = [(_TUN_CLASS_TYPES[c], np.arange(cs[c], cs[c + 1])) for c in range(4) if cs[c + 1] > cs[c]]
+        # "no inner decode" entries whose next type has a decoder all the same (a table edit
+        # that sends a protocol value to TCP, say): one batch per type
+        types = {int(t) for d in self.parser._decoders.values() for t in d.CanDecode()}
+        rest = {}
+        for j in range(cs[4], cs[5]):
+            t = pl["tunnels"][j]
+            if int(t["inner_len"]) and int(t["next_type"]) in types:
+                rest.setdefault(int(t["next_type"]), []).append(j)
+        return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
+
+    def _run_host(self, outputs, kinds, gre_checksum):
+        from .flows import Detunneler
+        b = self.batch
+        work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
+        level = 0
+        while work:
+            nxt = []
+            for first, index, offs, caps in work:
+                p = self._clone(first)
+                cfg = p._config(outputs)
+                dec = self.parser._host_decoder  # tests without a GPU put the decode oracle here
+                r = dec(p, b.data, offs, caps) if dec else p.ctx().decode_host(cfg, b.data, offs, caps, layouts=True)
+                pl = Detunneler.peel_host(b.data, offs, caps, r["records"], r["layouts"], cfg, kinds, gre_checksum)
+                part = self._add_part(level, first, index, offs, caps, r, pl)
+                for lt, js in self._next_work(part, level):
+                    nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
+            work, level = nxt, level + 1
+
+    def _run_device(self, outputs, kinds, gre_checksum):
+        import torch
+        from .flows import Detunneler
+        b = self.batch
+        ctx = self.parser.ctx()
+        dev = torch.device("cuda", ctx.device)
+        host = np.zeros((len(b.data) + 15) // 16 * 16 + 16, np.uint8)
+        host[:len(b.data)] = b.data
+        data = torch.from_numpy(host).to(dev)
+        det = Detunneler(max(len(b), 1), ctx.device)
+        try:
+            work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
+                     torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
+            level = 0
+            while work:
+                nxt = []
+                for first, index, offs, caps in work:
+                    n = len(index)
+                    p = self._clone(first)
+                    cfg = p._config(outputs)
+                    rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+                    err = torch.zeros(2 * n, dtype=torch.int32, device=dev)
+                    fl = torch.zeros(3 * n, dtype=torch.int64, device=dev)
+                    lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+                    ctx.decode_device(cfg, data, offs, caps, rec, err, fl, lay)
+                    out = det.peel(ctx, data, offs, caps, rec, lay, cfg, kinds, gre_checksum)
+                    torch.cuda.synchronize(dev)
+                    r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
+                             err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
+                             layouts=lay.cpu().numpy().view(_lib.LAYOUT_DTYPE))
+                    m = int(out["counts"][0].item())
+                    pl = dict(verdict=out["verdict"].cpu().numpy(),
+                              class_start=out["class_start"].cpu().numpy().view(np.uint32),
+                              counts=out["counts"].cpu().numpy().view(np.uint32),
+                              index=out["index"][:m].cpu().numpy().view(np.uint32),
+                              in_offsets=out["in_offsets"][:m].cpu().numpy().view(np.uint64),
+                              in_caplens=out["in_caplens"][:m].cpu().numpy().view(np.uint32),
+                              tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
+                                  _lib.TUNNEL_DTYPE))
+                    part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
+                                          caps.cpu().numpy().view(np.uint32), r, pl)
+                    for lt, js in self._next_work(part, level):
+                        if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
+                            io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
+                        else:
+                            sel = torch.from_numpy(js.astype(np.int64)).to(dev)
+                            io, ic = out["in_offsets"].index_select(0, sel), out["in_caplens"].index_select(0, sel)
+                        nxt.append((lt, index[pl["index"][js]], io, ic))
+                work, level = nxt, level + 1
+        finally:
+            det.close()
+
+    def __len__(self):
+        return len(self.batch)
+
+    def Level(self, k):
+        """The TunnelParts of level k (0: the outer decode), in class order."""
+        return self.levels[k]
+
+    def _tunnel(self, part, pos):
+        v = int(part.peel["verdict"][pos])
+        return part.peel["tunnels"][v] if v >= 0 else None
+
+    def Decoded(self, i):
+        out = []
+        for part, pos in self._chain[i]:
+            out += part.result.Decoded(pos)
+            t = self._tunnel(part, pos)
+            if t is not None and not int(t["err"]):
+                out.append(LayerType(_TUN_LAYER_TYPE[int(t["kind"])]))
+        return out
+
+    def Truncated(self, i):
+        tr = False
+        for part, pos in self._chain[i]:
+            t = self._tunnel(part, pos)
+            tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED))
+        return tr
+
+    def Err(self, i):
+        """The error value DecodeLayers returns for packet i with the tunnel
+        layers in the parser: the innermost level's."""
+        part, pos = self._chain[i][-1]
+        t = self._tunnel(part, pos)
+        if t is None:
+            return part.result.Err(pos)
+        code = int(t["err"])
+        if code:
+            buf = ctypes.create_string_buffer(256)
+            _lib.lib().gpk_tunnel_format_error(code, int(t["err_a0"]), int(t["err_a1"]), buf, 256)
+            msg = buf.value.decode()
+            if code in (2, 3, 4) and self.parser.IgnorePanic:
+                raise GoPanic(msg[len("panic: "):])
+            return GoError(msg)
+        typ = int(t["next_type"])
+        if int(t["inner_len"]) == 0 or typ == 0 or self.parser.IgnoreUnsupported:
+            return None
+        return UnsupportedLayerType(typ)
+
+    def Hydrate(self, i, decoded):
+        """Fill every layer struct of the parser, the tunnel layers included,
+        as after DecodeLayers(packet i, decoded): the levels are hydrated
+        outermost first, so each struct ends up holding its innermost instance
+        (one struct per type, parser.go:21-28). Returns the error value."""
+        p = self.parser
+        types = [int(t) for d in p._decoders.values() for t in d.CanDecode()]
+        if int(p.first) not in types:  # layers_decoder.go:12-16: decoded is not truncated
+            p.Truncated = False
+            return None if p.IgnoreUnsupported else UnsupportedLayerType(p.first)
+        for part, pos in self._chain[i]:
+            part.result.Hydrate(pos, [])
+            t = self._tunnel(part, pos)
+            if t is not None and not int(t["err"]):
+                p._tunnels[int(t["kind"])]._from_record(t, part.batch.packet(pos))
+        decoded[:] = self.Decoded(i)
+        p.Truncated = self.Truncated(i)
+        return self.Err(i)
 
 
 # ---- serialization: SerializeOptions / SerializeLayers (writer.go:43-218) for a batch

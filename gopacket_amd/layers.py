@@ -1,6 +1,8 @@
 """gopacket/layers surface for the hot path: LayerType and enum constants and
 the DecodingLayer structs Ethernet, Dot1Q, IPv4, IPv6, IPv6ExtensionSkipper,
-TCP, UDP (layers/{ethernet,dot1q,ip4,ip6,tcp,udp}.go).
+TCP, UDP (layers/{ethernet,dot1q,ip4,ip6,tcp,udp}.go), and the three tunnel
+layers GRE, VXLAN, Geneve (layers/{gre,vxlan,geneve}.go), which are filled from
+the gpk_tunnel record of gpk_tunnel_batch (include/gpk_tunnel.h).
 
 These structs are filled from device results, in one of two ways:
 - _fill(pkt, s, e, f): from the gpk_fields record the device wrote for the
@@ -56,6 +58,9 @@ LayerTypeDNS = _lt("DNS")
 LayerTypeTLS = _lt("TLS")
 LayerTypeModbus = _lt("Modbus")
 LayerTypeENIP = _lt("ENIP")
+LayerTypeGRE = _lt("GRE")
+LayerTypeVXLAN = _lt("VXLAN")
+LayerTypeGeneve = _lt("Geneve")
 # layertypes.go:200-206
 LayerClassIPv6Extension = LayerClass([LayerTypeIPv6HopByHop, LayerTypeIPv6Routing, LayerTypeIPv6Fragment,
                                       LayerTypeIPv6Destination])
@@ -1196,3 +1201,158 @@ def NewRUDPPortEndpoint(p):
 
 def NewUDPLitePortEndpoint(p):
     return _port_endpoint(EndpointUDPLitePort, int(p))
+
+
+# ---- tunnel layers: layers/gre.go, vxlan.go, geneve.go --------------------------
+# A DecodingLayerParser that holds one of these peels tunnel levels on the
+# device (gpk_tunnel_batch); the structs are filled from the level's gpk_tunnel
+# record and the packet bytes of that level (_from_record). `kind` values
+# above the device decoders' keep them apart in a container.
+class _TunnelLayer(BaseLayer):
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("tunnel layers decode through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+
+@dataclass
+class GRERouting:
+    """gre.go:27-34"""
+    AddressFamily: int = 0
+    SREOffset: int = 0
+    SRELength: int = 0
+    RoutingInformation: bytes = b""
+    Next: Optional["GRERouting"] = None
+
+
+class GRE(_TunnelLayer):
+    kind = 100 + _lib.TUN_GRE
+    tunnel_kind = _lib.TUN_GRE
+
+    def __init__(self):
+        self.ChecksumPresent = self.RoutingPresent = self.KeyPresent = self.SeqPresent = False
+        self.StrictSourceRoute = self.AckPresent = False
+        self.RecursionControl = self.Flags = self.Version = 0
+        self.Protocol = 0
+        self.Checksum = self.Offset = 0
+        self.Key = self.Seq = self.Ack = 0
+        self.GRERouting = None
+        self._csum = None
+
+    def LayerType(self):
+        return LayerTypeGRE
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeGRE])
+
+    def NextLayerType(self):
+        """gre.go:235-237"""
+        return EthernetTypeLayerType(self.Protocol)
+
+    def _from_record(self, t, pkt):
+        b0, b1 = int(t["raw0"]), int(t["raw1"])
+        self.ChecksumPresent, self.RoutingPresent = bool(b0 & 0x80), bool(b0 & 0x40)
+        self.KeyPresent, self.SeqPresent, self.StrictSourceRoute = bool(b0 & 0x20), bool(b0 & 0x10), bool(b0 & 0x08)
+        self.AckPresent = bool(b1 & 0x80)
+        self.RecursionControl, self.Flags, self.Version = b0 & 7, b1 >> 3, b1 & 7
+        self.Protocol = int(t["protocol"])
+        self.Checksum, self.Offset = int(t["gre_checksum"]), int(t["gre_offset"])
+        self.Key, self.Seq, self.Ack = int(t["gre_key"]), int(t["gre_seq"]), int(t["gre_ack"])
+        h, c = int(t["hdr_off"]), int(t["contents_len"])
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["inner_len"])]
+        self.GRERouting = None
+        o, sres = int(t["list_off"]), []
+        for _ in range(int(t["count"])):
+            sl = pkt[o + 3]
+            sres.append(GRERouting(_be16(pkt, o), pkt[o + 2], sl, pkt[o + 4:o + 4 + sl]))
+            o += 4 + sl
+        for sre in reversed(sres):
+            sre.Next, self.GRERouting = self.GRERouting, sre
+        st = int(t["status"])
+        self._csum = None
+        if st & _lib.TUN_ST_CSUM:
+            self._csum = (None, ChecksumVerificationResult(bool(st & _lib.TUN_ST_VALID), int(t["gre_correct"]),
+                                                           self.Checksum))
+
+    def VerifyChecksum(self):
+        """gre.go:239-250; the device's sum when the header has the C bit and
+        the level was peeled with gre_checksum, else computed here."""
+        if self._csum is not None:
+            return self._csum
+        from .gopacket import ComputeChecksum, FoldChecksum
+        correct = FoldChecksum((ComputeChecksum(self.Contents + self.Payload, 0) - self.Checksum) & 0xFFFFFFFF)
+        return None, ChecksumVerificationResult(not self.ChecksumPresent or correct == self.Checksum, correct,
+                                                self.Checksum)
+
+
+class VXLAN(_TunnelLayer):
+    kind = 100 + _lib.TUN_VXLAN
+    tunnel_kind = _lib.TUN_VXLAN
+
+    def __init__(self):
+        self.ValidIDFlag = self.GBPExtension = self.GBPDontLearn = self.GBPApplied = False
+        self.VNI = 0
+        self.GBPGroupPolicyID = 0
+
+    def LayerType(self):
+        return LayerTypeVXLAN
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeVXLAN])
+
+    def NextLayerType(self):
+        """vxlan.go:48-50"""
+        return LayerTypeEthernet
+
+    def _from_record(self, t, pkt):
+        bits = int(t["bits"])
+        self.ValidIDFlag, self.GBPExtension = bool(bits & _lib.TUN_VX_I), bool(bits & _lib.TUN_VX_G)
+        self.GBPDontLearn, self.GBPApplied = bool(bits & _lib.TUN_VX_D), bool(bits & _lib.TUN_VX_A)
+        self.VNI, self.GBPGroupPolicyID = int(t["vni"]), int(t["gbp_id"])
+        h, c = int(t["hdr_off"]), int(t["contents_len"])
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["inner_len"])]
+
+
+@dataclass
+class GeneveOption:
+    """geneve.go:45-51"""
+    Class: int = 0
+    Type: int = 0
+    Flags: int = 0
+    Length: int = 0
+    Data: bytes = b""
+
+
+class Geneve(_TunnelLayer):
+    kind = 100 + _lib.TUN_GENEVE
+    tunnel_kind = _lib.TUN_GENEVE
+
+    def __init__(self):
+        self.Version = self.OptionsLength = 0
+        self.OAMPacket = self.CriticalOption = False
+        self.Protocol = 0
+        self.VNI = 0
+        self.Options = []
+
+    def LayerType(self):
+        return LayerTypeGeneve
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeGeneve])
+
+    def NextLayerType(self):
+        """geneve.go:121-123"""
+        return EthernetTypeLayerType(self.Protocol)
+
+    def _from_record(self, t, pkt):
+        bits = int(t["bits"])
+        self.Version, self.OptionsLength = int(t["gn_version"]), int(t["gn_options_length"])
+        self.OAMPacket, self.CriticalOption = bool(bits & _lib.TUN_GN_O), bool(bits & _lib.TUN_GN_C)
+        self.Protocol, self.VNI = int(t["protocol"]), int(t["vni"])
+        h, c = int(t["hdr_off"]), int(t["contents_len"])
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["inner_len"])]
+        # the reference's walk (geneve.go:105-114): the offset is a uint8 and wraps
+        self.Options, o = [], 8
+        for _ in range(int(t["count"])):
+            b3 = pkt[h + o + 3]
+            ln = (b3 & 0x1f) * 4 + 4
+            self.Options.append(GeneveOption(_be16(pkt, h + o), pkt[h + o + 2], b3 >> 5, ln, pkt[h + o + 4:h + o + ln]))
+            o = (o + ln) & 0xff

@@ -14,6 +14,9 @@ Input: the device assembly of gpk_kernels.hip (hipcc -S --cuda-device-only,
 same flags as the library; the Makefile runs this beside check_stream_isa.py).
 
     python tools/check_scratch.py kernels.s      exit 1 on scratch in a default kernel
+    python tools/check_scratch.py --kernels=REGEX other.s
+                                                 the assembly of another source: exit 1 on
+                                                 scratch in any kernel whose name matches
 """
 import re
 import sys
@@ -56,6 +59,14 @@ def main(path):
     if not ks:
         print("check_scratch: no kernel metadata in %s" % path)
         return 1
+    named = [x.split("=", 1)[1] for x in sys.argv[1:] if x.startswith("--kernels=")]
+    if named:
+        sel = [k for k in ks if re.search(named[0], k[0])]
+        bad = [k for k in sel if k[1]]
+        for name, priv, vg in bad:
+            print("check_scratch: %s: %d bytes of scratch per lane (%d VGPRs)" % (name, priv, vg))
+        print("check_scratch: %d kernels matching %r, %d with scratch" % (len(sel), named[0], len(bad)))
+        return 1 if bad or not sel else 0
     bad = 0
     n = 0
     for name, priv, vg in ks:
