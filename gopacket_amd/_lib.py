@@ -97,6 +97,7 @@ EXPORTS = (
     "gpk_tpacket_set_ebpf", "gpk_tpacket_set_promiscuous", "gpk_tpacket_write", "gpk_tpacket_init_socket_stats",
     # include/gpk_flows.h
     "gpk_grouper_create", "gpk_grouper_destroy", "gpk_group_batch", "gpk_pack_batch", "gpk_decode_group_batch",
+    "gpk_grouper_hashes",
     # include/gpk_bpf.h
     "gpk_bpf_create", "gpk_bpf_destroy", "gpk_bpf_run", "gpk_bpf_select",
     # include/gpk_defrag.h
@@ -496,6 +497,7 @@ def lib():
         "gpk_tpacket_pump": ([vp, vp, vp, P(PumpOpts), PUMP_CB, vp, P(PumpStats)], c_int),
         "gpk_grouper_create": ([P(vp), c_int, u64], c_int),
         "gpk_grouper_destroy": ([vp], c_int),
+        "gpk_grouper_hashes": ([vp, u64, vp], c_int),
         "gpk_group_batch": ([vp, P(Batch), P(Results), c_int, u32, P(Groups), vp], c_int),
         "gpk_pack_batch": ([P(Batch), vp, u64, vp, vp, vp, vp], c_int),
         "gpk_decode_group_batch": ([vp, vp, P(Batch), P(Results), vp, c_int, P(Groups), vp], c_int),

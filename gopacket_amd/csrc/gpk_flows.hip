@@ -430,6 +430,16 @@ extern "C" int gpk_grouper_destroy(gpk_grouper* g) {
   return GPK_OK;
 }
 
+// test aid: the hashes of the last call's packets (unspecified where unkeyed)
+extern "C" int gpk_grouper_hashes(gpk_grouper* g, uint64_t n, uint64_t* out_host) {
+  if (!g || !out_host || n > g->cap) return GPK_EINVAL;
+  gpk::DeviceScope dscope(g->device);
+  if (dscope.err != hipSuccess) return GPK_EHIP;
+  if (hipDeviceSynchronize() != hipSuccess) return GPK_EHIP;
+  if (n && hipMemcpy(out_host, g->hash, n * 8, hipMemcpyDeviceToHost) != hipSuccess) return GPK_EHIP;
+  return GPK_OK;
+}
+
 extern "C" int gpk_group_batch(gpk_grouper* g, const gpk_batch* b, const gpk_results* r, int kind, uint32_t buckets,
                                const gpk_groups* o, void* stream) {
   if (!g || !b || !r || !o || !r->records || !o->group_of || !o->perm || !o->start || !o->first || !o->counts)

@@ -100,6 +100,15 @@ class Grouper:
                                                      int(kind), ctypes.byref(g), sp))
         return out
 
+    def hashes(self, n):
+        """gpk_grouper_hashes (a test aid): the 64-bit key hashes of the first n
+        packets of the last call, as a numpy uint64 array; unspecified where a
+        packet has no key. Synchronises the device."""
+        import numpy as np
+        out = np.zeros(int(n), np.uint64)
+        _lib.check(_lib.lib().gpk_grouper_hashes(self.h, int(n), out.ctypes.data))
+        return out
+
     @staticmethod
     def to_lists(out):
         """Host view: (groups: list of packet-index lists in group order, group_of list)."""

@@ -95,6 +95,16 @@ int gpk_group_batch(gpk_grouper* g, const gpk_batch* batch, const gpk_results* r
 int gpk_decode_group_batch(gpk_ctx* ctx, const gpk_parser* p, const gpk_batch* batch, const gpk_results* res,
                            gpk_grouper* g, int kind, const gpk_groups* out, void* stream);
 
+/* Test aid (like gpk_tunneler_set_sum_threshold): the 64-bit key hashes of the
+ * first n packets of the last gpk_group_batch / gpk_decode_group_batch call on
+ * this grouper, copied from its workspace to host memory, so that tests can
+ * choose keys by tag and home slot and notice when the hash changes. The value
+ * is unspecified for a packet without a key (group_of < 0); for NET_BUCKET it
+ * is the bucket. Synchronises the whole device before copying (the call it
+ * reads is asynchronous on a stream this function does not know). GPK_EINVAL
+ * for a null argument or n > max_packets. */
+int gpk_grouper_hashes(gpk_grouper* g, uint64_t n, uint64_t* out_host);
+
 /* Pack packets order[0..m) of a batch into a dense batch, in that order:
  * out_data receives their bytes back to back (it must hold their total
  * length), out_offsets[j] / out_caplens[j] index packet order[j]. The send

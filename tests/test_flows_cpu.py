@@ -108,3 +108,31 @@ def test_c_restatement_equals_python_oracle():
         groups, codes = FO.group(kind, pk, res["records"], res["layouts"], res["flows"], buckets)
         g, out = O.group_batch(kind, d, o, res["records"], res["layouts"], res["flows"], buckets)
         assert g == len(groups) and out.tolist() == codes, kind
+
+
+def test_grouphash_finder_and_edge_packets():
+    """tests/grouphash.py (the key chooser of tests/test_flows_table_gpu.py)
+    finds what those tests need: per kind at least 2 different keys sharing a
+    tag and a home slot of a 16-slot table, and 300 keys homed on the last
+    slots of a 1024-slot table; its candidates' hashes are those of the
+    oracle's key tuples. The window-edge packets of tests/flowcases.py start
+    their TCP and IPv4 headers where tests/test_flows_keys_gpu.py needs them."""
+    import grouphash as H
+    assert (H.table_size(8), H.table_size(512), H.table_size(1025)) == (16, 1024, 4096)
+    for kind in ("frag", "conn"):
+        pairs, stats = H.find_pairs(kind, 16)
+        assert len(pairs) >= 2 and stats["equal_tag"] >= len(pairs), stats
+        for a, b in pairs:
+            ha, hb = H.key_hash(H.candidate_key(kind, a)), H.key_hash(H.candidate_key(kind, b))
+            assert ha != hb and ha >> 28 == hb >> 28 and (ha ^ hb) & 15 == 0, (kind, a, b, stats)
+        for slots in ((1020, 1021, 1022, 1023), (1023,)):
+            cands, stats = H.find_homed(kind, 1024, slots, 300)
+            assert len(cands) == len(set(cands)) == 300, stats
+            assert {H.key_hash(H.candidate_key(kind, c)) & 1023 for c in cands} == set(slots), stats
+    for cases, slot, want in ((flowcases.window_connection4(), 5, set(range(34, 127, 4))),
+                              (flowcases.window_connection4in4(), 2, set(range(34, 91, 4))),
+                              (flowcases.window_defrag(), 2, set(range(14, 111, 4)))):
+        res = oracle_results([p for _, p in cases])
+        starts = res["layouts"]["start"][:, slot].tolist()
+        assert starts == [s for s, _ in cases] and set(starts) == want
+        assert not np.any((res["records"]["status"] & 0x7F) > 1)  # decoded whole, or stopped at the fragment

@@ -2,13 +2,18 @@
 (oracle/flows_oracle.py) run on the decode oracle's results: the same groups
 in the same order, the same packets in each, the same reason codes, on
 ip4defrag's test frames, tcpassembly's filter cases, fuzzed and golden
-packets and C6 traffic; at 8 M packets, properties the grouping must have."""
+packets and C6 traffic; at 8 M packets, properties the grouping must have.
+Then both entry points on batches that are not packed and ascending, at
+offsets past 4 GiB, at sizes around a wave and a block with all, none and
+some packets keyed, on one grouper used for many calls, and the GPK_EINVAL
+contract (tests/flowcheck.py holds the comparison with the oracle)."""
 import numpy as np
 import pytest
 
 import flowcases
 import pktutil
 from configs import CONFIGS, device_parser, oracle_parser
+from flowcheck import DEFRAG6, Decoded, check_fused, check_group
 from gopacket_amd import flows, synth
 from oracle import flows_oracle as FO
 
@@ -124,3 +129,187 @@ def test_large_batch_properties(gpu_ctx):
         seen.append(next(iter(keys)))
     assert len(set(seen)) == len(seen)  # distinct groups, distinct keys
     g.close()
+
+
+# ---------------------------------------------------------------------------
+# batch layouts, offsets past 4 GiB, sizes, grouper reuse, argument contract
+
+ALL_KINDS = KINDS + [(DEFRAG6, 8)]
+FUSED = (FO.CONNECTION, FO.DEFRAG)
+
+
+def edge_packets():
+    pk = [p for _, p in flowcases.inline_boundary_cases() + flowcases.ip_in_ip_cases() +
+          flowcases.useless_filter_cases()]
+    pk += list(flowcases.defrag_frames()[0].values()) + [f for _, f in flowcases.defrag_struct_cases()]
+    return pk + flowcases.connection_cases() + [p for _, p in flowcases.window_connection6()[::7]]
+
+
+@pytest.mark.parametrize("layout", ["sparse4k", "sparse_mix", "gapped", "shuffled", "reversed", "wave_shuffled"])
+def test_batch_layouts(gpu_ctx, layout):
+    """Both entry points on batches that are not packed and ascending (what a
+    tunnel level's in_offsets are): every kind through gpk_group_batch,
+    CONNECTION and DEFRAG through gpk_decode_group_batch, whose records and
+    flows equal a plain decode of the same batch."""
+    from test_gpu_parity import golden_packets, phase_b_layout
+    data, off, cap = phase_b_layout(pktutil.fuzz_packets(4242, 6000) + golden_packets() + edge_packets(), layout)
+    packets = [bytes(data[int(o):int(o) + int(c)]) for o, c in zip(off, cap)]
+    P = Decoded(gpu_ctx, packets, batch=(data, off, cap))
+    g = flows.Grouper(P.n)
+    for kind, buckets in ALL_KINDS:
+        check_group(g, P, kind, buckets, what=layout)
+        if kind in FUSED:
+            check_fused(g, P, kind, what=layout)
+    assert len(P.oracle(DEFRAG6)[0]) > 0  # the batch has IPv6 fragments
+    g.close()
+
+
+def test_offsets_past_4_GiB(gpu_ctx):
+    """The same packets at base (1 << 32) + 3 of a device buffer: gpk_group_batch,
+    gpk_decode_group_batch and gpk_pack_batch give what they give at base 0."""
+    import torch
+    packets = pktutil.fuzz_packets(4242, 2000) + edge_packets()
+    data, off, cap = pktutil.pack(packets)
+    base = (1 << 32) + 3
+    P0 = Decoded(gpu_ctx, packets)
+    big = torch.zeros(base + len(data) + 4096, dtype=torch.uint8, device="cuda")
+    big[base:base + len(data)] = P0.d
+    P1 = Decoded(gpu_ctx, packets, device_batch=(big, P0.o + base, P0.c), share=P0)
+    g = flows.Grouper(P0.n)
+    for kind, buckets in ALL_KINDS:
+        outs = [check_group(g, P, kind, buckets, what="base") for P in (P0, P1)]
+        if kind in FUSED:
+            outs += [check_fused(g, P, kind, what="base") for P in (P0, P1)]
+        for o in outs[1:]:
+            assert all(torch.equal(o[k], outs[0][k]) for k in ("group_of", "counts")), kind
+    g.close()
+    rng = np.random.default_rng(5)
+    order = torch.from_numpy(rng.integers(0, P0.n, 3000).astype(np.int32)).cuda()
+    a = flows.pack_batch(P0.d, P0.o, P0.c, order)
+    b = flows.pack_batch(big, P1.o, P1.c, order)
+    torch.cuda.synchronize()
+    want = np.concatenate([np.frombuffer(packets[i], np.uint8) for i in order.cpu().tolist()])
+    assert torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
+    for out_data in (a[0], b[0]):  # the wrapper's 16 spare bytes past the packets are not written
+        assert np.array_equal(out_data[:len(want)].cpu().numpy(), want)
+    del big, P1, b
+    torch.cuda.empty_cache()
+
+
+def sized_packets(kind, n, shape):
+    """n packets for `kind`: "all" keyed (about n / 3 keys), "none" keyed, or
+    "mixed": the first half keyed, the rest not (the last keyed packet is
+    followed by unkeyed ones)."""
+    keys = max(1, n // 3)
+
+    def keyed(i):
+        k = (i * 7) % keys
+        src = (10, 3, k >> 8, k & 255)
+        if kind == FO.DEFRAG:
+            return flowcases.eth_ip4(src, (10, 3, 0, 1), 0x100 + k, 1, 0, 28, proto=17, payload=bytes([i & 255]) * 8)
+        return flowcases.tcp_segment(src, (10, 3, 0, 1), 1000 + k, 80, 2 if i % 5 else 24, b"p" * (1 + i % 9))
+
+    def unkeyed(i):
+        if kind == FO.NET_BUCKET:
+            return flowcases.MAC + b"\x08\x06" + bytes([i & 255]) * 28
+        if kind == FO.DEFRAG:
+            return flowcases.tcp_segment((10, 3, 0, 2), (10, 3, 0, 1), 1000 + i % 50, 80, 2)
+        if i % 2:  # ACK-only without payload: GPK_GROUP_USELESS
+            return flowcases.tcp_segment((10, 3, 0, 2), (10, 3, 0, 1), 1000 + i % 50, 80, 16)
+        return flowcases.eth_ip4((10, 3, 0, 2), (10, 3, 0, 1), i & 0xFFFF, 1, 0, 28, proto=17, payload=b"u" * 8)
+
+    cut = {"all": n, "none": 0, "mixed": (n + 1) // 2}[shape]
+    return [keyed(i) if i < cut else unkeyed(i) for i in range(n)]
+
+
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 255, 256, 257, 1025])
+def test_sizes_and_keyed_shapes(gpu_ctx, n):
+    """Batch sizes around a wave and a block, in a grouper of exactly that size:
+    all packets keyed, none keyed (counts [0, 0], start[0] 0), keyed packets
+    followed by unkeyed ones. The outputs start poisoned; flowcheck.compare
+    asserts group_of, perm[:K], start[:G + 1], first[:G], counts, and that
+    perm[K:] is a permutation of the unkeyed packets."""
+    g = flows.Grouper(n)
+    for kind, buckets in KINDS[:3]:
+        for shape in ("all", "none", "mixed"):
+            P = Decoded(gpu_ctx, sized_packets(kind, n, shape))
+            groups, codes, _ = P.oracle(kind, buckets)
+            keyed = sum(c >= 0 for c in codes)  # the shape is what it claims to be
+            assert keyed == {"all": n, "none": 0, "mixed": (n + 1) // 2}[shape], (kind, shape, keyed)
+            out = check_group(g, P, kind, buckets, what=(n, shape))
+            if shape == "none":
+                assert out["counts"].cpu().tolist() == [0, 0] and int(out["start"][0]) == 0
+            if kind in FUSED:
+                check_fused(g, P, kind, what=(n, shape))
+    g.close()
+
+
+def test_one_grouper_many_calls(gpu_ctx):
+    """One Grouper(1025), never re-created, for 1025 (its capacity), 1, 257 and
+    1025 packets, every kind and both entry points in turn on workspace the
+    call before left behind; the first call repeated at the end gives its
+    first result."""
+    import torch
+    g = flows.Grouper(1025)
+    fuzz = pktutil.fuzz_packets(606, 1025 - len(edge_packets())) + edge_packets()
+    batches = [Decoded(gpu_ctx, fuzz), Decoded(gpu_ctx, [flowcases.connection_cases()[0]]),
+               Decoded(gpu_ctx, sized_packets(FO.DEFRAG, 257, "mixed")),
+               Decoded(gpu_ctx, sized_packets(FO.CONNECTION, 1025, "all"))]
+    assert [P.n for P in batches] == [1025, 1, 257, 1025]
+    first = check_group(g, batches[0], FO.CONNECTION, what="first")
+    step = 0
+    for rounds in range(2):
+        for P in batches:
+            for kind, buckets in ALL_KINDS:
+                step += 1
+                if kind in FUSED and step % 2:
+                    check_fused(g, P, kind, what=step)
+                else:
+                    check_group(g, P, kind, buckets, what=step)
+    for kind in FUSED:
+        for P in batches:
+            check_fused(g, P, kind, what="fused")
+    again = check_group(g, batches[0], FO.CONNECTION, what="again")
+    assert all(torch.equal(first[k], again[k]) for k in first)
+    g.close()
+
+
+def test_argument_contract(gpu_ctx):
+    """Every misuse returns GPK_EINVAL and leaves the grouper usable."""
+    import ctypes
+
+    import torch
+    from gopacket_amd import _lib
+
+    def einval(f, *a, **kw):
+        with pytest.raises(_lib.GpkError, match=r"\(%d\)" % _lib.GPK_EINVAL):
+            f(*a, **kw)
+
+    P = Decoded(gpu_ctx, flowcases.connection_cases()[:4])
+    P5 = Decoded(gpu_ctx, flowcases.connection_cases()[:5])
+    g = flows.Grouper(4)
+
+    def fused(P, kind):
+        rec = torch.zeros(P.n * 16, dtype=torch.uint8, device="cuda")
+        return g.decode_group(gpu_ctx, P.parser, P.d, P.o, P.c, rec, None, None, kind=kind)
+
+    misuses = [lambda: g.group(P5.d, P5.o, P5.c, P5.rec, P5.lay, P5.fl, kind=FO.CONNECTION),  # n = max_packets + 1
+               lambda: fused(P5, FO.CONNECTION)]
+    misuses += [lambda b=b: g.group(P.d, P.o, P.c, P.rec, P.lay, P.fl, kind=FO.NET_BUCKET, buckets=b)
+                for b in (0, 3, 1 << 17)]
+    misuses += [lambda k=k: g.group(P.d, P.o, P.c, P.rec, P.lay, P.fl, kind=k) for k in (0, 5, 99)]  # unknown kinds
+    misuses += [lambda: g.group(P.d, P.o, P.c, P.rec, P.lay, None, kind=FO.NET_BUCKET),   # no flows
+                lambda: g.group(P.d, P.o, P.c, P.rec, None, P.fl, kind=FO.CONNECTION),    # no layouts
+                lambda: g.group(P.d, P.o, P.c, P.rec, None, P.fl, kind=FO.DEFRAG),
+                lambda: fused(P, DEFRAG6), lambda: fused(P, FO.NET_BUCKET), lambda: fused(P, 0)]
+    for k, f in enumerate(misuses):
+        einval(f)
+        check_group(g, P, FO.CONNECTION, what=("after misuse", k))
+    check_fused(g, P, FO.CONNECTION, what="after misuses")
+    g.close()
+    for cap in (0, 1 << 28):
+        h = ctypes.c_void_p()
+        assert _lib.lib().gpk_grouper_create(ctypes.byref(h), 0, cap) == _lib.GPK_EINVAL and not h
+        einval(flows.Grouper, cap)
+    assert _lib.lib().gpk_grouper_create(None, 0, 8) == _lib.GPK_EINVAL
+    assert _lib.lib().gpk_grouper_hashes(None, 0, None) == _lib.GPK_EINVAL
