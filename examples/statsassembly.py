@@ -29,6 +29,13 @@ the last batch (main.go:210), and the statistics gain the reference's
 out-of-order and skipped counts. Reassembly.Seen is the capture time of the
 chunk's source packet.
 
+--flush-older-than SECONDS (with --device-assembly) is the reference's periodic
+flush (main.go:156-161: every so often, FlushOlderThan(now - 2 minutes)) in
+capture time, because a wall-clock trigger over a file is not reproducible:
+before each batch, FlushOlderThan(first timestamp of the batch - SECONDS) runs
+on the device (a timed Assembler, include/gpk_tcpasm.h), so connections that
+went quiet are flushed and closed while the file is read, not only at the end.
+
   python examples/statsassembly.py tests/golden/test_ethernet.pcap -v
 """
 import argparse
@@ -140,20 +147,22 @@ class DeviceStatsStream:
     is the capture time of the first chunk (the reference takes time.Now() in
     New, which a capture file cannot give)."""
 
-    def __init__(self, net, transport, log):
+    def __init__(self, net, transport, log, unit=1.0):
         self.net, self.transport, self.log = net, transport, log
+        self.unit = unit  # seconds per unit of Reassembly.Seen (a timed Assembler hands back int64 ns)
         self.bytes = self.packets = self.outOfOrder = self.skipped = 0
         self.start = self.end = None
         self.sawStart = self.sawEnd = self.complete = False
 
     def Reassembled(self, reassemblies):
         for r in reassemblies:
+            seen = r.Seen * self.unit
             if self.start is None:
-                self.start = self.end = r.Seen
-            if r.Seen < self.end:
+                self.start = self.end = seen
+            if seen < self.end:
                 self.outOfOrder += 1
             else:
-                self.end = r.Seen
+                self.end = seen
             self.bytes += len(r.Bytes)
             self.packets += 1
             if r.Skip > 0:
@@ -171,10 +180,12 @@ class DeviceStatsStream:
                                  "%.1f" % (self.packets / secs) if secs > 0 else "+Inf", self.skipped))
 
 
-def run_device_assembly(path, count=-1, batch=1 << 16, max_pages=0, log=print):
+def run_device_assembly(path, count=-1, batch=1 << 16, max_pages=0, log=print, flush_older_than=None):
     """main.go:119-211 with tcpassembly on the device. Returns (streams in the
     order of their New calls, packets read, bytes of the packets decoded
-    without error)."""
+    without error). flush_older_than: seconds; before each batch
+    FlushOlderThan(the batch's first timestamp - flush_older_than) runs, the
+    capture-time form of main.go:156-161."""
     import numpy as np
     from gopacket_amd import _lib, gopacket, layers, pcapgo, tcpassembly
     parser = gopacket.NewDecodingLayerParser(layers.LayerTypeEthernet, layers.Ethernet(), layers.Dot1Q(),
@@ -185,11 +196,12 @@ def run_device_assembly(path, count=-1, batch=1 << 16, max_pages=0, log=print):
     class Factory(tcpassembly.StreamFactory):
         def New(self, net, transport):
             log("new stream %s:%s started" % (net, transport))
-            made.append(DeviceStatsStream(net, transport, log))
+            made.append(DeviceStatsStream(net, transport, log, 1e-9 if timed else 1.0))
             return made[-1]
 
+    timed = flush_older_than is not None
     assembler = tcpassembly.NewAssembler(tcpassembly.NewStreamPool(Factory()), ctx=parser.ctx(),
-                                         parser=parser._config(), max_packets=2 * batch + 1024)
+                                         parser=parser._config(), max_packets=2 * batch + 1024, timed=timed)
     assembler.MaxBufferedPagesPerConnection = max_pages
     read = byte_count = 0
     start = time.time()
@@ -213,7 +225,13 @@ def run_device_assembly(path, count=-1, batch=1 << 16, max_pages=0, log=print):
             for i in np.flatnonzero((res.records["status"] & _lib.ST_ERR_MASK) != 0):
                 log("error decoding packet: %s" % res.Err(int(i)).Error())
             byte_count += int(pb.caplens[ok].sum())
-            seen = b.ci["ts_sec"][ok].astype(np.float64) + b.ci["ts_nsec"][ok] * 1e-9
+            if timed:
+                seen = b.ci["ts_sec"][ok].astype(np.int64) * 1000000000 + b.ci["ts_nsec"][ok].astype(np.int64)
+                if len(seen):
+                    flushed, closed = assembler.FlushOlderThan(int(seen[0]) - int(flush_older_than * 1e9))
+                    log("forced flush: %d flushed, %d closed" % (flushed, closed))  # main.go:159-160
+            else:
+                seen = b.ci["ts_sec"][ok].astype(np.float64) + b.ci["ts_nsec"][ok] * 1e-9
             assembler.AssembleBatch(pb.data, pb.offsets[ok], pb.caplens[ok], seen)
     assembler.FlushAll()
     assembler.close()
@@ -262,9 +280,13 @@ def main():
                     help="reassemble the TCP streams on the device (gopacket_amd.tcpassembly)")
     ap.add_argument("--max-pages", type=int, default=0,
                     help="MaxBufferedPagesPerConnection for --device-assembly (0: no limit)")
+    ap.add_argument("--flush-older-than", type=float, default=None, metavar="SECONDS",
+                    help="with --device-assembly: before each batch, FlushOlderThan(its first timestamp - SECONDS)")
     a = ap.parse_args()
+    if a.flush_older_than is not None and not a.device_assembly:
+        ap.error("--flush-older-than needs --device-assembly")
     if a.device_assembly:
-        run_device_assembly(a.file, a.c, a.batch, a.max_pages)
+        run_device_assembly(a.file, a.c, a.batch, a.max_pages, flush_older_than=a.flush_older_than)
         return
     run(a.file, a.c, a.batch, a.v, a.device_groups)
 

@@ -101,11 +101,11 @@ EXPORTS = (
     # include/gpk_bpf.h
     "gpk_bpf_create", "gpk_bpf_destroy", "gpk_bpf_run", "gpk_bpf_select",
     # include/gpk_defrag.h
-    "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch",
+    "gpk_defragger_create", "gpk_defragger_destroy", "gpk_defrag_batch", "gpk_defrag_batch_timed",
     # include/gpk_defrag6.h
-    "gpk_defragger6_create", "gpk_defragger6_destroy", "gpk_defrag6_batch",
+    "gpk_defragger6_create", "gpk_defragger6_destroy", "gpk_defrag6_batch", "gpk_defrag6_batch_timed",
     # include/gpk_tcpasm.h
-    "gpk_tcpasm_create", "gpk_tcpasm_destroy", "gpk_tcpasm_batch",
+    "gpk_tcpasm_create", "gpk_tcpasm_destroy", "gpk_tcpasm_batch", "gpk_tcpasm_batch_timed",
     # include/gpk_capwrite.h
     "gpk_capwriter_create", "gpk_capwriter_destroy", "gpk_capwriter_interfaces", "gpk_capwriter_set_interfaces",
     "gpk_capwrite_file_header", "gpk_capwrite_section_header", "gpk_capwrite_add_interface",
@@ -145,6 +145,13 @@ class Datagrams(ctypes.Structure):
                 ("data_cap", ctypes.c_uint64)]
 
 
+class DefragTime(ctypes.Structure):
+    """gpk_defrag_time and gpk_defrag6_time (the same layout): timestamps in,
+    DiscardOlderThan(t) after the batch, key times and counts out."""
+    _fields_ = [("seen", ctypes.c_void_p), ("discard", ctypes.c_uint32), ("t", ctypes.c_int64),
+                ("pending_seen", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
 # include/gpk_defrag6.h constants
 DEFRAG6_HELD, DEFRAG6_CARRIED = -32, -33
 DEFRAG6_MAX_LIST = 8192
@@ -174,6 +181,16 @@ class TcpasmOpts(ctypes.Structure):
     """gpk_tcpasm_opts"""
     _fields_ = [("max_pages", ctypes.c_uint32), ("flush", ctypes.c_uint32), ("carried", ctypes.c_uint64),
                 ("carry_code", ctypes.c_void_p), ("carry_seq", ctypes.c_void_p)]
+
+
+class TcpasmTime(ctypes.Structure):
+    """gpk_tcpasm_time"""
+    _fields_ = [("seen", ctypes.c_void_p), ("flush_older", ctypes.c_uint32), ("t", ctypes.c_int64),
+                ("conn_last_seen", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+TCPASM_FLUSH_T, TCPASM_FLUSH_T_CLOSE_ALL = 1, 2  # gpk_tcpasm_time.flush_older
+TIME_ZERO = -(1 << 63)  # Go's zero time.Time as the reassemblers see it: INT64_MIN
 
 
 class TcpStreams(ctypes.Structure):
@@ -504,12 +521,17 @@ def lib():
         "gpk_defragger_create": ([P(vp), c_int, u64], c_int),
         "gpk_defragger_destroy": ([vp], c_int),
         "gpk_defrag_batch": ([vp, P(Batch), P(Results), P(Groups), P(Datagrams), vp], c_int),
+        "gpk_defrag_batch_timed": ([vp, P(Batch), P(Results), P(Groups), P(Datagrams), P(DefragTime), vp], c_int),
         "gpk_defragger6_create": ([P(vp), c_int, u64], c_int),
         "gpk_defragger6_destroy": ([vp], c_int),
         "gpk_defrag6_batch": ([vp, P(Batch), P(Results), P(Groups), u64, P(Datagrams6), vp], c_int),
+        "gpk_defrag6_batch_timed": ([vp, P(Batch), P(Results), P(Groups), u64, P(Datagrams6), P(DefragTime), vp],
+                                    c_int),
         "gpk_tcpasm_create": ([P(vp), c_int, u64], c_int),
         "gpk_tcpasm_destroy": ([vp], c_int),
         "gpk_tcpasm_batch": ([vp, P(Batch), P(Results), P(Groups), P(TcpasmOpts), P(TcpStreams), vp], c_int),
+        "gpk_tcpasm_batch_timed": ([vp, P(Batch), P(Results), P(Groups), P(TcpasmOpts), P(TcpStreams), P(TcpasmTime),
+                                    vp], c_int),
         "gpk_capwriter_create": ([P(vp), c_int, c_int, u64], c_int),
         "gpk_capwriter_destroy": ([vp], c_int),
         "gpk_capwriter_interfaces": ([vp], c_int),

@@ -25,6 +25,14 @@
 //                    header. A datagram is split at its fragments, so no work
 //                    item is longer than one fragment's payload (64 KB at most,
 //                    64 wave steps; 2 at MTU 1500).
+//   time (gpk_defrag_batch_timed) adds four small kernels around the scans and
+//   leaves the five above as they are: `pending` lists exactly the fragments
+//   that stamped LastSeen, in arrival order, so a key's LastSeen is seen[] of
+//   its last pending packet. mark_kernel finds that packet per key (an atomic
+//   maximum over the key's pending packets, and their count), key_kernel turns
+//   it into the key's LastSeen and the discard decision and counts, drop_kernel
+//   takes a discarded key's packets out of `pending` before the scan, and
+//   seen_kernel writes pending_seen behind it.
 // Every list state variable is computed identically by all 64 lanes from
 // shuffled values, so the control flow around ballots, shuffles and barriers
 // is wave-uniform; blocks of the plan kernel are one wave.
@@ -307,6 +315,62 @@ __global__ void __launch_bounds__(256) finish_kernel(const int32_t* group_of, ui
   }
 }
 
+// ---- time: LastSeen and DiscardOlderThan (defrag.go:138-149, :249)
+struct TimeWork {
+  uint32_t* key_last;  // [n] per group: 1 + its last pending packet, 0 if it has none
+  uint32_t* key_cnt;   // [n] per group: its pending packets
+  int64_t* key_seen;   // [n] per group: LastSeen
+  uint32_t* dead;      // [n] per group: discarded
+};
+
+__global__ void __launch_bounds__(256) mark_kernel(const int32_t* group_of, uint64_t n, IsPending pend, TimeWork tw) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t g = group_of[i];
+  if (g < 0 || !pend((uint32_t)i)) return;
+  atomicMax(&tw.key_last[g], (uint32_t)i + 1);
+  atomicAdd(&tw.key_cnt[g], 1u);
+}
+
+__global__ void __launch_bounds__(256) key_kernel(const uint32_t* gcounts, uint64_t n, TimeWork tw,
+                                                  gpk_defrag_time tm) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = g < n && g < gcounts[0];
+  uint32_t dead = 0, dropped = 0;
+  if (live) {
+    const uint32_t last = tw.key_last[g];
+    int64_t ks = INT64_MIN;  // a key flushed by the end of the batch: nothing pending, nothing to discard
+    if (last) {
+      ks = tm.seen[last - 1];
+      dead = tm.discard && ks < tm.t;
+      if (dead) dropped = tw.key_cnt[g];
+    }
+    tw.key_seen[g] = ks;
+    tw.dead[g] = dead;
+  }
+  const uint32_t keys = (uint32_t)__popcll(__ballot(dead != 0));
+  for (int m = 32; m; m >>= 1) dropped += (uint32_t)__shfl_xor((int)dropped, m);
+  if ((threadIdx.x & 63) == 0 && keys) {
+    atomicAdd((unsigned long long*)&tm.counts[0], (unsigned long long)keys);
+    atomicAdd((unsigned long long*)&tm.counts[1], (unsigned long long)dropped);
+  }
+}
+
+__global__ void __launch_bounds__(256) drop_kernel(const int32_t* group_of, uint64_t n, TimeWork tw, uint32_t* inst) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t g = group_of[i];
+  if (g >= 0 && tw.dead[g]) inst[i] = 0;  // no longer counted for a live key
+}
+
+__global__ void __launch_bounds__(256) seen_kernel(const int32_t* group_of, uint64_t n, IsPending pend,
+                                                   const uint32_t* ppos, TimeWork tw, int64_t* pending_seen) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int32_t g = group_of[i];
+  if (g >= 0 && pend((uint32_t)i)) pending_seen[ppos[i]] = tw.key_seen[g];
+}
+
 using gpk::copy_bytes;  // gpk_copy.h
 
 struct CopyArgs {
@@ -371,6 +435,7 @@ struct gpk_defragger {
   int device = 0;
   uint64_t cap = 0;
   Work w{};
+  TimeWork tw{};
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
 };
@@ -380,7 +445,8 @@ namespace {
 void free_all(gpk_defragger* d) {
   for (void* p : {(void*)d->w.info, (void*)d->w.inst, (void*)d->w.final_inst, (void*)d->w.dsize, (void*)d->w.dhigh,
                   (void*)d->w.dnum, (void*)d->w.ddst, (void*)d->w.ppos, (void*)d->w.seg_pkt, (void*)d->w.seg_skip,
-                  (void*)d->w.seg_dst, (void*)d->w.seg_owner, d->tmp})
+                  (void*)d->w.seg_dst, (void*)d->w.seg_owner, (void*)d->tw.key_last, (void*)d->tw.key_cnt,
+                  (void*)d->tw.key_seen, (void*)d->tw.dead, d->tmp})
     if (p) (void)hipFree(p);
 }
 
@@ -413,6 +479,9 @@ extern "C" int gpk_defragger_create(gpk_defragger** out, int device, uint64_t ma
        hipMalloc((void**)&w.ddst, n * 8) == hipSuccess && hipMalloc((void**)&w.ppos, n * 4) == hipSuccess &&
        hipMalloc((void**)&w.seg_pkt, n * 4) == hipSuccess && hipMalloc((void**)&w.seg_skip, n * 4) == hipSuccess &&
        hipMalloc((void**)&w.seg_dst, n * 4) == hipSuccess && hipMalloc((void**)&w.seg_owner, n * 4) == hipSuccess &&
+       hipMalloc((void**)&d->tw.key_last, n * 4) == hipSuccess &&
+       hipMalloc((void**)&d->tw.key_cnt, n * 4) == hipSuccess &&
+       hipMalloc((void**)&d->tw.key_seen, n * 8) == hipSuccess && hipMalloc((void**)&d->tw.dead, n * 4) == hipSuccess &&
        hipMalloc(&d->tmp, d->tmp_bytes) == hipSuccess;
   if (!ok) {
     free_all(d);
@@ -432,8 +501,11 @@ extern "C" int gpk_defragger_destroy(gpk_defragger* d) {
   return GPK_OK;
 }
 
-extern "C" int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
-                                const gpk_datagrams* o, void* stream) {
+namespace {
+
+// tm == nullptr: gpk_defrag_batch
+int defrag_run(gpk_defragger* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g, const gpk_datagrams* o,
+               const gpk_defrag_time* tm, void* stream) {
   if (!d || !b || !r || !g || !o || !o->counts) return GPK_EINVAL;
   const uint64_t n = b->n;
   if (n > d->cap) return GPK_EINVAL;
@@ -441,10 +513,12 @@ extern "C" int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* b, const gpk_
             !o->verdict || !o->last || !o->length || !o->offsets || !o->caplens || !o->payload_off || !o->pending ||
             (!o->data && o->data_cap)))
     return GPK_EINVAL;
+  if (tm && (!tm->counts || (n && (!tm->seen || !tm->pending_seen)))) return GPK_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   gpk::DeviceScope dscope(d->device);
   if (dscope.err != hipSuccess) return GPK_EHIP;
   if (hipMemsetAsync(o->counts, 0, 4 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
+  if (tm && hipMemsetAsync(tm->counts, 0, 2 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
   if (n == 0) return GPK_OK;
   const Work& w = d->w;
   const dim3 blk(256), grd((unsigned)((n + 255) / 256));
@@ -455,6 +529,14 @@ extern "C" int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* b, const gpk_
   hipLaunchKernelGGL(plan_kernel<kSmallCap>, dim3(pblocks), dim3(64), 0, s, pa);
   hipLaunchKernelGGL(plan_kernel<GPK_DEFRAG_MAX_LIST>, dim3(std::min(pblocks, 4096u)), dim3(64), 0, s, pa);
   const IsPending pend{w.inst, w.final_inst, g->group_of};
+  if (tm) {
+    const TimeWork& tw = d->tw;
+    if (hipMemsetAsync(tw.key_last, 0, n * 4, s) != hipSuccess || hipMemsetAsync(tw.key_cnt, 0, n * 4, s) != hipSuccess)
+      return GPK_EHIP;
+    hipLaunchKernelGGL(mark_kernel, grd, blk, 0, s, g->group_of, n, pend, tw);
+    hipLaunchKernelGGL(key_kernel, grd, blk, 0, s, g->counts, n, tw, *tm);
+    if (tm->discard) hipLaunchKernelGGL(drop_kernel, grd, blk, 0, s, g->group_of, n, tw, w.inst);
+  }
   size_t tb = d->tmp_bytes;
   if (hipcub::DeviceScan::ExclusiveSum(d->tmp, tb, DnumIt(w.dsize, NonZero()), w.dnum, (int)n, s) != hipSuccess)
     return GPK_EHIP;
@@ -466,8 +548,22 @@ extern "C" int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* b, const gpk_
                                        (int)n, s) != hipSuccess)
     return GPK_EHIP;
   hipLaunchKernelGGL(finish_kernel, grd, blk, 0, s, g->group_of, n, w, pend, *o);
+  if (tm) hipLaunchKernelGGL(seen_kernel, grd, blk, 0, s, g->group_of, n, pend, w.ppos, d->tw, tm->pending_seen);
   const uint64_t want = (n + 3) / 4;  // 4 waves per block, one segment per wave per pass
   const CopyArgs ca{b->data, b->offsets, g->counts, w, o->data, o->data_cap};
   hipLaunchKernelGGL(copy_kernel, dim3((unsigned)std::min<uint64_t>(want, 65536)), blk, 0, s, ca);
   return hipGetLastError() == hipSuccess ? GPK_OK : GPK_EHIP;
+}
+
+}  // namespace
+
+extern "C" int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
+                                const gpk_datagrams* o, void* stream) {
+  return defrag_run(d, b, r, g, o, nullptr, stream);
+}
+
+extern "C" int gpk_defrag_batch_timed(gpk_defragger* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
+                                      const gpk_datagrams* o, const gpk_defrag_time* tm, void* stream) {
+  if (!tm) return GPK_EINVAL;
+  return defrag_run(d, b, r, g, o, tm, stream);
 }

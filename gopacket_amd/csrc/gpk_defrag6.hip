@@ -35,6 +35,11 @@
 //                    needs no materialised segment lists, and a datagram's first
 //                    byte is four dependent loads away. The last wave writes the
 //                    header.
+//   time (gpk_defrag6_batch_timed) adds three small kernels around the scans
+//   and leaves the five above as they are: every call stamps its key, so a
+//   key's time is seen[] of the key's last packet. key6_kernel reads it per key
+//   and decides the discard, drop6_kernel takes a discarded key's fragments out
+//   of `listed` before the pending scan, seen6_kernel writes pending_seen.
 // Every list state variable is computed identically by all 64 lanes from
 // shuffled values, so the control flow around ballots, shuffles and barriers
 // is wave-uniform; blocks of the plan kernel are one wave.
@@ -269,6 +274,47 @@ __global__ void __launch_bounds__(256) finish6_kernel(const int32_t* group_of, c
   }
 }
 
+// ---- time: the deferred stamp (defrag.go:84-87) and DiscardOlderThan (:183-194)
+struct TimeWork {
+  int64_t* key_seen;  // [n] per group: the key's time
+  uint32_t* dead;     // [n] per group: discarded
+};
+
+__global__ void __launch_bounds__(256) key6_kernel(const uint32_t* perm, const uint32_t* start, const uint32_t* gcounts,
+                                                   uint64_t n, TimeWork tw, gpk_defrag6_time tm) {
+  const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t dead = 0;
+  if (g < n && g < gcounts[0]) {
+    // perm is ascending inside a key and every call stamps: the key's last packet made the last stamp
+    const int64_t ks = tm.seen[perm[start[g + 1] - 1]];
+    dead = tm.discard && ks < tm.t;
+    tw.key_seen[g] = ks;
+    tw.dead[g] = dead;
+  }
+  const uint32_t keys = (uint32_t)__popcll(__ballot(dead != 0));
+  if ((threadIdx.x & 63) == 0 && keys) atomicAdd((unsigned long long*)&tm.counts[0], (unsigned long long)keys);
+}
+
+__global__ void __launch_bounds__(256) drop6_kernel(const int32_t* group_of, uint64_t n, TimeWork tw, uint32_t* listed,
+                                                    uint64_t* counts) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  bool drop = false;
+  if (i < n) {
+    const int32_t g = group_of[i];
+    drop = g >= 0 && tw.dead[g] && listed[i];
+    if (drop) listed[i] = 0;
+  }
+  const uint32_t c = (uint32_t)__popcll(__ballot(drop));
+  if ((threadIdx.x & 63) == 0 && c) atomicAdd((unsigned long long*)&counts[1], (unsigned long long)c);
+}
+
+__global__ void __launch_bounds__(256) seen6_kernel(const int32_t* group_of, uint64_t n, const uint32_t* listed,
+                                                    const uint32_t* ppos, TimeWork tw, int64_t* pending_seen) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  if (listed[i]) pending_seen[ppos[i]] = tw.key_seen[group_of[i]];  // listed: keyed
+}
+
 struct MoveArgs {
   const uint8_t* data;
   const uint64_t* offsets;
@@ -343,6 +389,7 @@ struct gpk_defragger6 {
   int device = 0;
   uint64_t cap = 0;
   Work w{};
+  TimeWork tw{};
   void* tmp = nullptr;
   size_t tmp_bytes = 0;
 };
@@ -352,7 +399,7 @@ namespace {
 void free_all(gpk_defragger6* d) {
   for (void* p : {(void*)d->w.info, (void*)d->w.listed, (void*)d->w.dsize, (void*)d->w.dpay, (void*)d->w.dhead,
                   (void*)d->w.dnum, (void*)d->w.ddst, (void*)d->w.ppos, (void*)d->w.fin, (void*)d->w.fin_len,
-                  (void*)d->w.desc, d->tmp})
+                  (void*)d->w.desc, (void*)d->tw.key_seen, (void*)d->tw.dead, d->tmp})
     if (p) (void)hipFree(p);
 }
 
@@ -384,6 +431,7 @@ extern "C" int gpk_defragger6_create(gpk_defragger6** out, int device, uint64_t 
        hipMalloc((void**)&w.dnum, n * 4) == hipSuccess &&
        hipMalloc((void**)&w.ddst, n * 8) == hipSuccess && hipMalloc((void**)&w.ppos, n * 4) == hipSuccess &&
        hipMalloc((void**)&w.fin, n * 4) == hipSuccess && hipMalloc((void**)&w.fin_len, n * 4) == hipSuccess &&
+       hipMalloc((void**)&d->tw.key_seen, n * 8) == hipSuccess && hipMalloc((void**)&d->tw.dead, n * 4) == hipSuccess &&
        hipMalloc(&d->tmp, d->tmp_bytes) == hipSuccess;
   if (!ok) {
     free_all(d);
@@ -403,8 +451,11 @@ extern "C" int gpk_defragger6_destroy(gpk_defragger6* d) {
   return GPK_OK;
 }
 
-extern "C" int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
-                                 uint64_t carry, const gpk_datagrams6* o, void* stream) {
+namespace {
+
+// tm == nullptr: gpk_defrag6_batch
+int defrag6_run(gpk_defragger6* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g, uint64_t carry,
+                const gpk_datagrams6* o, const gpk_defrag6_time* tm, void* stream) {
   if (!d || !b || !r || !g || !o || !o->counts) return GPK_EINVAL;
   const uint64_t n = b->n;
   if (n > d->cap || carry > n) return GPK_EINVAL;
@@ -412,10 +463,12 @@ extern "C" int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* b, const gp
             !o->verdict || !o->last || !o->head || !o->length || !o->offsets || !o->caplens || !o->payload_off ||
             !o->pending || (!o->data && o->data_cap)))
     return GPK_EINVAL;
+  if (tm && (!tm->counts || (n && (!tm->seen || !tm->pending_seen)))) return GPK_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   gpk::DeviceScope dscope(d->device);
   if (dscope.err != hipSuccess) return GPK_EHIP;
   if (hipMemsetAsync(o->counts, 0, 4 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
+  if (tm && hipMemsetAsync(tm->counts, 0, 2 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
   if (n == 0) return GPK_OK;
   const Work& w = d->w;
   const dim3 blk(256), grd((unsigned)((n + 255) / 256));
@@ -425,6 +478,10 @@ extern "C" int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* b, const gp
   const PlanArgs pa{g->perm, g->start, g->counts, (uint32_t)carry, o->verdict, w};
   hipLaunchKernelGGL(plan6_kernel<kSmallCap>, dim3(pblocks), dim3(64), 0, s, pa);
   hipLaunchKernelGGL(plan6_kernel<GPK_DEFRAG6_MAX_LIST>, dim3(std::min(pblocks, 4096u)), dim3(64), 0, s, pa);
+  if (tm) {
+    hipLaunchKernelGGL(key6_kernel, grd, blk, 0, s, g->perm, g->start, g->counts, n, d->tw, *tm);
+    if (tm->discard) hipLaunchKernelGGL(drop6_kernel, grd, blk, 0, s, g->group_of, n, d->tw, w.listed, tm->counts);
+  }
   size_t tb = d->tmp_bytes;
   if (hipcub::DeviceScan::ExclusiveSum(d->tmp, tb, DnumIt(w.dsize, NonZero()), w.dnum, (int)n, s) != hipSuccess)
     return GPK_EHIP;
@@ -435,8 +492,23 @@ extern "C" int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* b, const gp
   if (hipcub::DeviceScan::ExclusiveSum(d->tmp, tb, (const uint32_t*)w.listed, w.ppos, (int)n, s) != hipSuccess)
     return GPK_EHIP;
   hipLaunchKernelGGL(finish6_kernel, grd, blk, 0, s, g->group_of, g->start, n, w, *o);
+  if (tm) hipLaunchKernelGGL(seen6_kernel, grd, blk, 0, s, g->group_of, n, w.listed, w.ppos, d->tw, tm->pending_seen);
   // one block per datagram, striding: a packet returns at most one
   const MoveArgs ma{b->data, b->offsets, w, o->counts, o->data, o->data_cap};
   hipLaunchKernelGGL(move6_kernel, dim3((unsigned)std::min<uint64_t>(n, 65536)), blk, 0, s, ma);
   return hipGetLastError() == hipSuccess ? GPK_OK : GPK_EHIP;
+}
+
+}  // namespace
+
+extern "C" int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
+                                 uint64_t carry, const gpk_datagrams6* o, void* stream) {
+  return defrag6_run(d, b, r, g, carry, o, nullptr, stream);
+}
+
+extern "C" int gpk_defrag6_batch_timed(gpk_defragger6* d, const gpk_batch* b, const gpk_results* r,
+                                       const gpk_groups* g, uint64_t carry, const gpk_datagrams6* o,
+                                       const gpk_defrag6_time* tm, void* stream) {
+  if (!tm) return GPK_EINVAL;
+  return defrag6_run(d, b, r, g, carry, o, tm, stream);
 }

@@ -21,7 +21,17 @@
 //                     instantiation), and for the others whatever lies beyond
 //                     is in the key's slice of the page workspace. Chunks go to the key's
 //                     slice of the chunk workspace in delivery order, which is
-//                     stream-major inside a key.
+//                     stream-major inside a key. With time (a template parameter
+//                     beside SMALL: the untimed instantiations compile from the
+//                     code they always had) the key also keeps lastSeen, the
+//                     maximum of its calls' timestamps. Nothing reads it before
+//                     the end of the batch, so every lane keeps the maximum of
+//                     the calls it held (one compare per step, off the chain
+//                     that carries nextSeq) and one wave maximum per key joins
+//                     them at the end; a new connection resets all lanes. A wave
+//                     maximum per in-order run cost 0.5 us per 64-packet step.
+//                     FlushWithOptions{T} runs where FlushAll does, with the
+//                     same pop / send / close.
 //   4. hipcub scans   stream numbers, chunk bases, byte bases (by creating
 //                     packet), pending bases (by group)
 //   5. finish_kernel  per-stream and per-group arrays, stream_of, counts
@@ -129,6 +139,7 @@ struct PlanArgs {
   int32_t* verdict;
   int64_t* conn_seq;
   Work w;
+  gpk_tcpasm_time tm;  // read by the timed instantiations only
 };
 
 // The first kSmallCap positions of the list of the key a block (one wave) works on.
@@ -325,7 +336,16 @@ struct Key {
   }
 };
 
-template <bool SMALL>
+// max over the wave of v (lanes that do not take part pass INT64_MIN)
+__device__ __forceinline__ int64_t wave_max(int64_t v) {
+  for (int m = 32; m; m >>= 1) {
+    const int64_t o = (int64_t)__shfl_xor((long long)v, m);
+    if (o > v) v = o;
+  }
+  return v;
+}
+
+template <bool SMALL, bool TIMED>
 __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
   const uint32_t lane = threadIdx.x;
   const uint32_t G = a.gcounts[0], K = a.gcounts[1];
@@ -346,18 +366,27 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
     // ahead, the index it hangs on two steps ahead
     uint32_t pkt_a = 0, pkt_b = 0;
     uint4 inf_a = make_uint4(0, 0, 0, 0);
+    // TIMED: this lane's share of conn.lastSeen (the maximum over the calls it held), and seen[] one step
+    // ahead like info
+    int64_t lane_seen = INT64_MIN, sn_a = INT64_MIN;
     if (lane < k) {
       pkt_a = a.perm[s + lane];
       inf_a = a.w.info[pkt_a];
+      if constexpr (TIMED) sn_a = a.tm.seen[pkt_a];
     }
     if (64 + lane < k) pkt_b = a.perm[s + 64 + lane];
     for (uint32_t c0 = 0; c0 < k; c0 += 64) {
       const uint32_t cnt = k - c0 < 64 ? k - c0 : 64;
       const uint32_t pkt = pkt_a;
       const uint4 inf = inf_a;
+      const int64_t sn = sn_a;
       pkt_a = pkt_b;
       inf_a = make_uint4(0, 0, 0, 0);
-      if (c0 + 64 + lane < k) inf_a = a.w.info[pkt_a];
+      sn_a = INT64_MIN;
+      if (c0 + 64 + lane < k) {
+        inf_a = a.w.info[pkt_a];
+        if constexpr (TIMED) sn_a = a.tm.seen[pkt_a];
+      }
       pkt_b = 0;
       if (c0 + 128 + lane < k) pkt_b = a.perm[s + c0 + 128 + lane];
       int32_t my_v = 0;
@@ -399,6 +428,9 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
             c.next = ((int64_t)(uint32_t)((uint32_t)c.next + total));
             c.schunks += run;
             c.used += run;
+            if constexpr (TIMED) {  // every call of the run: if lastSeen.Before(ts) lastSeen = ts (:567-569)
+              if (lane >= t && lane < first && lane_seen < sn) lane_seen = sn;
+            }
             t = first;
             continue;
           }
@@ -418,6 +450,7 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
           v = GPK_TCPASM_EBADCARRY;
           if ((fw & kCarryConn) && !(fw & kCarryPage) && !c.open) {
             c.open_conn(tp, a.carry_seq[tp]);
+            if constexpr (TIMED) lane_seen = a.tm.seen[tp];  // the carried connection's lastSeen
             v = GPK_TCPASM_CARRIED;
           } else if ((fw & kCarryPage) && !(fw & kCarryConn) && c.open && pg < pages) {
             if (lane == 0) c.put_page(c.head + c.len, seq, tp, plen, pg, pages, end);
@@ -429,7 +462,13 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
         } else if (!c.open && !syn && plen == 0) {  // getConnection(key, end = true) (:552-560)
           v = GPK_TCPASM_NOCONN;
         } else {
-          if (!c.open) c.open_conn(tp, -1);
+          if (!c.open) {
+            c.open_conn(tp, -1);
+            if constexpr (TIMED) lane_seen = INT64_MIN;  // a new connection starts fresh (include/gpk_tcpasm.h)
+          }
+          if constexpr (TIMED) {  // :567-569
+            if (lane == t && lane_seen < sn) lane_seen = sn;
+          }
           cr_t = c.cr;
           bool direct = true;
           if (c.next == -1) {
@@ -480,6 +519,32 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
         c.pop(call);
         c.send(call);
       }
+    }
+    if constexpr (TIMED) {
+      const int64_t last_seen = wave_max(lane_seen);
+      if (a.tm.flush_older) {  // FlushWithOptions{T, CloseAll} (:238-269) on this connection
+        bool flushed = false, closed = false;
+        uint32_t r = 0;
+        // only the FIRST page's Seen is tested; what is contiguous behind it goes out whatever its age
+        while (c.open && c.len && a.tm.seen[c.ld(s_pkt, c.gpkt, c.head)] < a.tm.t) {
+          const uint32_t call = GPK_TCPASM_CALL_FLUSH | r++;
+          c.nret = 0;
+          c.last_end = false;
+          c.pop(call);   // skipFlush (:648-660)
+          c.send(call);
+          flushed = true;
+          if (!c.open) closed = true;
+        }
+        if (a.tm.flush_older == 2 && c.open && !c.len && last_seen < a.tm.t) {
+          c.close(GPK_TCPASM_CALL_FLUSH | r);
+          flushed = closed = true;
+        }
+        if (lane == 0) {
+          if (flushed) atomicAdd((unsigned long long*)&a.tm.counts[0], 1ull);
+          if (closed) atomicAdd((unsigned long long*)&a.tm.counts[1], 1ull);
+        }
+      }
+      if (lane == 0) a.tm.conn_last_seen[g] = c.open ? last_seen : INT64_MIN;
     }
     if (c.open) {
       c.end_stream(GPK_TCPASM_OPEN);
@@ -739,9 +804,13 @@ extern "C" int gpk_tcpasm_destroy(gpk_tcpasm* d) {
   return GPK_OK;
 }
 
-extern "C" int gpk_tcpasm_batch(gpk_tcpasm* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
-                                const gpk_tcpasm_opts* op, const gpk_tcp_streams* o, void* stream) {
+namespace {
+
+// tm == nullptr: gpk_tcpasm_batch
+int tcpasm_run(gpk_tcpasm* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g, const gpk_tcpasm_opts* op,
+               const gpk_tcp_streams* o, const gpk_tcpasm_time* tm, void* stream) {
   if (!d || !b || !r || !g || !op || !o || !o->counts) return GPK_EINVAL;
+  if (tm && (!tm->counts || tm->flush_older > 2 || (tm->flush_older && op->flush))) return GPK_EINVAL;
   const uint64_t n = b->n;
   if (n > d->cap || op->carried > n) return GPK_EINVAL;
   if (op->carried && (!op->carry_code || !op->carry_seq)) return GPK_EINVAL;
@@ -750,10 +819,12 @@ extern "C" int gpk_tcpasm_batch(gpk_tcpasm* d, const gpk_batch* b, const gpk_res
             !o->stream_chunk0 || !o->stream_data0 || !o->conn_seq || !o->conn_stream ||
             (o->chunk_cap && (!o->chunks || !o->pend_pkt || !o->pend_page)) || (!o->data && o->data_cap)))
     return GPK_EINVAL;
+  if (tm && n && (!tm->seen || !tm->conn_last_seen)) return GPK_EINVAL;
   hipStream_t s = (hipStream_t)stream;
   gpk::DeviceScope dscope(d->device);
   if (dscope.err != hipSuccess) return GPK_EHIP;
   if (hipMemsetAsync(o->counts, 0, 8 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
+  if (tm && hipMemsetAsync(tm->counts, 0, 2 * sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
   if (o->stream_chunk0 && hipMemsetAsync(o->stream_chunk0, 0, sizeof(uint32_t), s) != hipSuccess) return GPK_EHIP;
   if (o->stream_data0 && hipMemsetAsync(o->stream_data0, 0, sizeof(uint64_t), s) != hipSuccess) return GPK_EHIP;
   if (n == 0) return GPK_OK;
@@ -775,9 +846,15 @@ extern "C" int gpk_tcpasm_batch(gpk_tcpasm* d, const gpk_batch* b, const gpk_res
     return GPK_EHIP;
   // one wave per key, striding: at most n keys
   const unsigned pblocks = (unsigned)std::min<uint64_t>(n, 1u << 18);
-  const PlanArgs pa{g->perm, g->start, g->counts, op->carry_seq, op->max_pages, op->flush, o->verdict, o->conn_seq, w};
-  hipLaunchKernelGGL(plan_kernel<true>, dim3(pblocks), dim3(64), 0, s, pa);
-  hipLaunchKernelGGL(plan_kernel<false>, dim3(std::min(pblocks, 4096u)), dim3(64), 0, s, pa);
+  const PlanArgs pa{g->perm,       g->start,   g->counts,   op->carry_seq, op->max_pages,
+                    op->flush,     o->verdict, o->conn_seq, w,             tm ? *tm : gpk_tcpasm_time{}};
+  if (tm) {
+    hipLaunchKernelGGL((plan_kernel<true, true>), dim3(pblocks), dim3(64), 0, s, pa);
+    hipLaunchKernelGGL((plan_kernel<false, true>), dim3(std::min(pblocks, 4096u)), dim3(64), 0, s, pa);
+  } else {
+    hipLaunchKernelGGL((plan_kernel<true, false>), dim3(pblocks), dim3(64), 0, s, pa);
+    hipLaunchKernelGGL((plan_kernel<false, false>), dim3(std::min(pblocks, 4096u)), dim3(64), 0, s, pa);
+  }
   tb = d->tmp_bytes;
   if (hipcub::DeviceScan::ExclusiveSum(d->tmp, tb, (const uint32_t*)w.s_made, w.snum, (int)n, s) != hipSuccess)
     return GPK_EHIP;
@@ -798,4 +875,18 @@ extern "C" int gpk_tcpasm_batch(gpk_tcpasm* d, const gpk_batch* b, const gpk_res
   const EmitArgs ea{b->data, b->offsets, g->counts, w, *o};
   hipLaunchKernelGGL(emit_kernel, dim3((unsigned)std::min<uint64_t>(want, 65536)), blk, 0, s, ea);
   return hipGetLastError() == hipSuccess ? GPK_OK : GPK_EHIP;
+}
+
+}  // namespace
+
+extern "C" int gpk_tcpasm_batch(gpk_tcpasm* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
+                                const gpk_tcpasm_opts* op, const gpk_tcp_streams* o, void* stream) {
+  return tcpasm_run(d, b, r, g, op, o, nullptr, stream);
+}
+
+extern "C" int gpk_tcpasm_batch_timed(gpk_tcpasm* d, const gpk_batch* b, const gpk_results* r, const gpk_groups* g,
+                                      const gpk_tcpasm_opts* op, const gpk_tcp_streams* o, const gpk_tcpasm_time* tm,
+                                      void* stream) {
+  if (!tm) return GPK_EINVAL;
+  return tcpasm_run(d, b, r, g, op, o, tm, stream);
 }

@@ -18,15 +18,20 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
   Defragmenter(max_packets).defrag(...)    gpk_defrag_batch (include/gpk_defrag.h):
                                            ip4defrag's reassembly of a DEFRAG-grouped
                                            batch (defrag.go:113-132,214-326)
-  IPv4Defragmenter(ctx, parser, n)         the same over a stream of batches
+  IPv4Defragmenter(ctx, parser, n)         the same over a stream of batches; timed=True keeps
+                                           LastSeen and gives discard_older_than (:138-149)
   Defragmenter6(max_packets).defrag(...)   gpk_defrag6_batch (include/gpk_defrag6.h):
                                            ip6defrag's reassembly of a DEFRAG6-grouped
                                            batch (ip6defrag/defrag.go:82-178)
-  IPv6Defragmenter(ctx, parser, n)         the same over a stream of batches
+  IPv6Defragmenter(ctx, parser, n)         the same over a stream of batches; timed=True keeps
+                                           the keys' times and gives discard_older_than (:183-194)
+  timestamps_ns(capinfo)                   a CAPINFO_DTYPE array as int64 ns on the device
   Assembler(max_packets).assemble(...)     gpk_tcpasm_batch (include/gpk_tcpasm.h):
                                            tcpassembly's reassembly of a CONNECTION-grouped
                                            batch (assembly.go:536-783, FlushAll :279-290)
-  TCPAssembler(ctx, parser, n)             the same over a stream of batches
+  TCPAssembler(ctx, parser, n)             the same over a stream of batches; timed=True keeps
+                                           lastSeen and page.Seen and gives flush_older_than
+                                           (FlushWithOptions, :238-274)
   Serializer(max_packets).serialize(...)   gpk_serialize_batch (include/gpk_serialize.h):
                                            gopacket.SerializeLayers for a decoded batch, from
                                            its layouts and (edited) fields records
@@ -148,6 +153,30 @@ def pack_batch(data, offsets, caplens, order, total_bytes=None, stream=None):
     return out_d, out_o[:m], out_c[:m]
 
 
+def timestamps_ns(capinfo, device=None):
+    """The capture timestamps of a _lib.CAPINFO_DTYPE array (a capture reader's
+    or replay's per-packet info) as time.Time.UnixNano(): an int64 device
+    tensor of ts_sec * 10^9 + ts_nsec, what the timed reassemblers take."""
+    import numpy as np
+    import torch
+    ci = np.asarray(capinfo)
+    ns = ci["ts_sec"].astype(np.int64) * 1000000000 + ci["ts_nsec"].astype(np.int64)
+    return torch.from_numpy(np.ascontiguousarray(ns)).to("cuda" if device is None else device)
+
+
+def _time_arg(n, dev, seen, discard_older_than):
+    """-> (DefragTime, pending_seen, time_counts) for a timed defrag call."""
+    import torch
+    if seen.dtype != torch.int64 or seen.numel() != n:
+        raise ValueError("seen: one int64 timestamp per packet")
+    seen = seen.contiguous()
+    ps = torch.empty(max(n, 1), dtype=torch.int64, device=dev)
+    tc = torch.zeros(2, dtype=torch.int64, device=dev)
+    t = _lib.DefragTime(seen.data_ptr() if n else None, 0 if discard_older_than is None else 1,
+                        0 if discard_older_than is None else int(discard_older_than), ps.data_ptr(), tc.data_ptr())
+    return t, ps, tc, seen
+
+
 HELD, EHOLE, EINVALID, EMAXLEN, EPANIC = (_lib.DEFRAG_HELD, _lib.DEFRAG_EHOLE, _lib.DEFRAG_EINVALID,
                                           _lib.DEFRAG_EMAXLEN, _lib.DEFRAG_EPANIC)
 
@@ -156,17 +185,24 @@ class Defragmenter:
     """gpk_defrag_batch (include/gpk_defrag.h): the datagrams
     ip4defrag.DefragIPv4 would have returned for a decoded, DEFRAG-grouped
     batch, every packet's verdict and the fragments still waiting. One call
-    behaves like a fresh NewIPv4Defragmenter() fed the batch in order; no
-    timeouts (DiscardOlderThan)."""
+    behaves like a fresh NewIPv4Defragmenter() fed the batch in order. With
+    `seen` (gpk_defrag_batch_timed) the keys keep LastSeen and
+    DiscardOlderThan can run after the batch."""
 
     def __init__(self, max_packets, device=0):
         self.h = ctypes.c_void_p()
         _lib.check(_lib.lib().gpk_defragger_create(ctypes.byref(self.h), device, int(max_packets)))
         self.max_packets = int(max_packets)
 
-    def defrag(self, data, offsets, caplens, records, layouts, groups, data_cap=None, out_data=None, stream=None):
+    def defrag(self, data, offsets, caplens, records, layouts, groups, data_cap=None, out_data=None, stream=None,
+               seen=None, discard_older_than=None):
         """Device tensors in: the batch, its records and layouts, and `groups`
-        (Grouper.group(kind=DEFRAG) of it). Returns a dict of device tensors:
+        (Grouper.group(kind=DEFRAG) of it). seen: int64 ns per packet
+        (DefragIPv4WithTimestamp's t; for a carried fragment its key's LastSeen);
+        with it the result also has pending_seen (LastSeen of pending[k]'s key)
+        and time_counts[2] (keys discarded, packets dropped), and
+        discard_older_than=t runs DiscardOlderThan(t) after the batch: pending and
+        counts[1] are the survivors. Returns a dict of device tensors:
         verdict[n], last/length/offsets/caplens/payload_off (n entries, counts[0]
         used), pending (counts[1] used), counts[4] (datagrams, pending, bytes
         needed, overflow) and data. data_cap defaults to the batch's data size,
@@ -198,8 +234,15 @@ class Defragmenter:
                            out["offsets"].data_ptr(), out["caplens"].data_ptr(), out["payload_off"].data_ptr(),
                            out["pending"].data_ptr(), out["counts"].data_ptr(), out_data.data_ptr(), cap)
         sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        _lib.check(_lib.lib().gpk_defrag_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
-                                               ctypes.byref(d), sp))
+        if seen is None:
+            if discard_older_than is not None:
+                raise ValueError("discard_older_than needs seen")
+            _lib.check(_lib.lib().gpk_defrag_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                   ctypes.byref(d), sp))
+        else:
+            t, out["pending_seen"], out["time_counts"], seen = _time_arg(n, dev, seen, discard_older_than)
+            _lib.check(_lib.lib().gpk_defrag_batch_timed(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                         ctypes.byref(d), ctypes.byref(t), sp))
         out["verdict"] = out["verdict"][:n]
         return out
 
@@ -222,14 +265,21 @@ class IPv4Defragmenter:
     reference's state. Each call decodes (with layouts), groups and
     reassembles pending + new packets; verdicts and `last` are mapped back to
     the caller's indices (a datagram can only be completed by a new packet).
-    No timeouts: flush() is the caller's DiscardOlderThan."""
 
-    def __init__(self, ctx, parser, max_packets, device=0):
+    timed=False keeps no time: flush() is then the caller's only
+    DiscardOlderThan. timed=True: defrag() takes the packets' timestamps
+    (int64 ns, greater than INT64_MIN), every key keeps its LastSeen on the
+    device beside its fragments, and discard_older_than(t) is
+    DiscardOlderThan(t)."""
+
+    def __init__(self, ctx, parser, max_packets, device=0, timed=False):
         self.ctx, self.parser = ctx, parser
         self.max_packets = int(max_packets)
+        self.timed = bool(timed)
         self.grouper = Grouper(self.max_packets, device)
         self.defragmenter = Defragmenter(self.max_packets, device)
         self._pending = None  # (data, offsets, caplens) on the device
+        self._pending_seen = None  # timed: int64[pending], the LastSeen of each carried fragment's key
 
     @property
     def pending_count(self):
@@ -238,14 +288,35 @@ class IPv4Defragmenter:
     def flush(self):
         """Forget every waiting fragment; returns how many there were."""
         k = self.pending_count
-        self._pending = None
+        self._pending = self._pending_seen = None
         return k
 
-    def defrag(self, data, offsets, caplens):
+    def discard_older_than(self, t):
+        """DiscardOlderThan(t), t in int64 ns: the keys whose LastSeen < t are
+        forgotten with their fragments. Returns the number of keys discarded
+        (the reference's return value). timed=True only."""
+        import torch
+        if not self.timed:
+            raise NotImplementedError("discard_older_than: time is out of scope unless timed=True")
+        if not self.pending_count:
+            return 0
+        dev = self._pending[1].device
+        out = self._step(torch.empty(0, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev),
+                         torch.empty(0, dtype=torch.int64, device=dev), int(t))
+        return out["time_counts"][0]
+
+    def defrag(self, data, offsets, caplens, timestamps=None):
         """One batch of packets (device tensors: uint8 data, int64 offsets,
-        int32 caplens). Returns Defragmenter.defrag's dict for the caller's
-        packets, with `verdict` and `last` in the caller's indices and
-        counts/pending on the host: datagrams, data, offsets, caplens, ..."""
+        int32 caplens; timed: int64 ns timestamps, one per packet). Returns
+        Defragmenter.defrag's dict for the caller's packets, with `verdict` and
+        `last` in the caller's indices and counts/pending on the host:
+        datagrams, data, offsets, caplens, ..."""
+        if self.timed != (timestamps is not None):
+            raise ValueError("timestamps go with timed=True, and only with it")
+        return self._step(data, offsets, caplens, timestamps, None)
+
+    def _step(self, data, offsets, caplens, timestamps, discard_t):
         import torch
         dev = offsets.device
         P = self.pending_count
@@ -255,20 +326,24 @@ class IPv4Defragmenter:
             data = torch.cat([pd, data])
             offsets = torch.cat([po, offsets + base])
             caplens = torch.cat([pc, caplens])
+            if self.timed:
+                timestamps = torch.cat([self._pending_seen, timestamps])
         n = offsets.numel()
         if n > self.max_packets:
             raise ValueError("pending + batch exceed max_packets")
         if n == 0:
             e32, e64 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
             return dict(verdict=e32, last=e32, length=e32, offsets=e64, caplens=e32, payload_off=e32, pending=e32,
-                        counts=[0, 0, 0, 0], datagrams=0, data=torch.empty(0, dtype=torch.uint8, device=dev))
+                        counts=[0, 0, 0, 0], datagrams=0, data=torch.empty(0, dtype=torch.uint8, device=dev),
+                        **(dict(pending_seen=e64, time_counts=[0, 0]) if self.timed else {}))
         rec = torch.zeros(max(n, 1) * 16, dtype=torch.uint8, device=dev)
         lay = torch.zeros(max(n, 1) * 64, dtype=torch.uint8, device=dev)
         flw = torch.zeros(max(n, 1) * 3, dtype=torch.int64, device=dev)
         st = torch.cuda.current_stream()
         self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
         groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=DEFRAG, stream=st)
-        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, stream=st)
+        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, stream=st,
+                                       seen=timestamps if self.timed else None, discard_older_than=discard_t)
         counts = out["counts"].cpu().tolist()
         D, K = counts[0], counts[1]
         pend = out["pending"][:K]
@@ -278,6 +353,9 @@ class IPv4Defragmenter:
             self._pending = (d2[:total], o2, c2)
         else:
             self._pending = None
+        if self.timed:
+            self._pending_seen = out["pending_seen"][:K].clone() if K else None
+            out.update(pending_seen=out["pending_seen"][:K], time_counts=out["time_counts"].cpu().tolist())
         v = out["verdict"][P:]
         out.update(verdict=v, last=out["last"][:D] - P, length=out["length"][:D], offsets=out["offsets"][:D],
                    caplens=out["caplens"][:D], payload_off=out["payload_off"][:D], pending=pend - P,
@@ -298,7 +376,8 @@ class Defragmenter6:
     batch, every packet's verdict and the fragments it holds. One call behaves
     like a fresh NewIPv6Defragmenter() fed the batch in order. A key is never
     flushed (a completed datagram comes again with every later call on its
-    key); no time (DiscardOlderThan)."""
+    key). With `seen` (gpk_defrag6_batch_timed) the keys keep their time and
+    DiscardOlderThan can run after the batch."""
 
     def __init__(self, max_packets, device=0):
         self.h = ctypes.c_void_p()
@@ -306,10 +385,15 @@ class Defragmenter6:
         self.max_packets = int(max_packets)
 
     def defrag(self, data, offsets, caplens, records, layouts, groups, carry=0, data_cap=None, out_data=None,
-               stream=None):
+               stream=None, seen=None, discard_older_than=None):
         """Device tensors in: the batch, its records and layouts, and `groups`
         (Grouper.group(kind=DEFRAG6) of it). The calls of the first `carry`
-        packets build state only (verdict CARRIED6, nothing emitted). Returns a
+        packets build state only (verdict CARRIED6, nothing emitted). seen: int64
+        ns per packet (the call's time; for a carry packet its key's time); with
+        it the result also has pending_seen (the time of pending[k]'s key) and
+        time_counts[2] (keys discarded, listed fragments dropped), and
+        discard_older_than=t runs DiscardOlderThan(t) after the batch: pending and
+        counts[1] are the survivors. Returns a
         dict of device tensors: verdict[n], last/head/length/offsets/caplens/
         payload_off (n entries, counts[0] used), pending (counts[1] used),
         counts[4] (datagrams, pending, bytes needed, overflow) and data.
@@ -343,8 +427,15 @@ class Defragmenter6:
                                                           "payload_off", "pending", "counts")],
                             out_data.data_ptr(), cap)
         sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        _lib.check(_lib.lib().gpk_defrag6_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g), int(carry),
-                                                ctypes.byref(d), sp))
+        if seen is None:
+            if discard_older_than is not None:
+                raise ValueError("discard_older_than needs seen")
+            _lib.check(_lib.lib().gpk_defrag6_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                    int(carry), ctypes.byref(d), sp))
+        else:
+            t, out["pending_seen"], out["time_counts"], seen = _time_arg(n, dev, seen, discard_older_than)
+            _lib.check(_lib.lib().gpk_defrag6_batch_timed(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                          int(carry), ctypes.byref(d), ctypes.byref(t), sp))
         out["verdict"] = out["verdict"][:n]
         return out
 
@@ -371,20 +462,26 @@ class IPv6Defragmenter:
     from a carried packet of an earlier batch (-1 is the last of them); its
     bytes are in the datagram all the same.
 
-    The reference never removes a key (only DiscardOlderThan does, and time is
-    out of scope), so by default the state grows without bound, as the
-    reference's does: flush() is the caller's DiscardOlderThan. Scope decision
+    The reference never removes a key (only DiscardOlderThan does), so by
+    default the state grows without bound, as the reference's does when
+    DiscardOlderThan is never called. timed=False keeps no time: flush() is
+    then the caller's only DiscardOlderThan. timed=True: defrag() takes the
+    packets' timestamps (int64 ns; they play the reference's time.Now()),
+    every key keeps the time of its last call on the device beside its
+    fragments, and discard_older_than(t) is DiscardOlderThan(t). Scope decision
     that departs from the reference: with drop_completed=True a key that
     returned a datagram in a call is not carried into the next one, so it does
     not return that datagram again in later batches and its state is freed."""
 
-    def __init__(self, ctx, parser, max_packets, device=0, drop_completed=False):
+    def __init__(self, ctx, parser, max_packets, device=0, drop_completed=False, timed=False):
         self.ctx, self.parser = ctx, parser
         self.max_packets = int(max_packets)
         self.drop_completed = bool(drop_completed)
+        self.timed = bool(timed)
         self.grouper = Grouper(self.max_packets, device)
         self.defragmenter = Defragmenter6(self.max_packets, device)
         self._pending = None  # (data, offsets, caplens) on the device
+        self._pending_seen = None  # timed: int64[pending], the time of each carried fragment's key
 
     @property
     def pending_count(self):
@@ -393,14 +490,35 @@ class IPv6Defragmenter:
     def flush(self):
         """Forget every held fragment; returns how many there were."""
         k = self.pending_count
-        self._pending = None
+        self._pending = self._pending_seen = None
         return k
 
-    def defrag(self, data, offsets, caplens):
+    def discard_older_than(self, t):
+        """DiscardOlderThan(t), t in int64 ns: the keys whose last call was
+        before t are forgotten with their fragments. Returns the number of keys
+        discarded (the reference's return value). timed=True only."""
+        import torch
+        if not self.timed:
+            raise NotImplementedError("discard_older_than: time is out of scope unless timed=True")
+        if not self.pending_count:
+            return 0
+        dev = self._pending[1].device
+        out = self._step(torch.empty(0, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev),
+                         torch.empty(0, dtype=torch.int64, device=dev), int(t))
+        return out["time_counts"][0]
+
+    def defrag(self, data, offsets, caplens, timestamps=None):
         """One batch of packets (device tensors: uint8 data, int64 offsets,
-        int32 caplens). Returns Defragmenter6.defrag's dict for the caller's
-        packets, with `verdict`, `last` and `head` in the caller's indices and
-        counts/pending on the host: datagrams, data, offsets, caplens, ..."""
+        int32 caplens; timed: int64 ns timestamps, one per packet). Returns
+        Defragmenter6.defrag's dict for the caller's packets, with `verdict`,
+        `last` and `head` in the caller's indices and counts/pending on the host:
+        datagrams, data, offsets, caplens, ..."""
+        if self.timed != (timestamps is not None):
+            raise ValueError("timestamps go with timed=True, and only with it")
+        return self._step(data, offsets, caplens, timestamps, None)
+
+    def _step(self, data, offsets, caplens, timestamps, discard_t):
         import torch
         dev = offsets.device
         P = self.pending_count
@@ -410,6 +528,8 @@ class IPv6Defragmenter:
             data = torch.cat([pd, data])
             offsets = torch.cat([po, offsets + base])
             caplens = torch.cat([pc, caplens])
+            if self.timed:
+                timestamps = torch.cat([self._pending_seen, timestamps])
         n = offsets.numel()
         if n > self.max_packets:
             raise ValueError("pending + batch exceed max_packets")
@@ -417,26 +537,32 @@ class IPv6Defragmenter:
             e32, e64 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
             return dict(verdict=e32, last=e32, head=e32, length=e32, offsets=e64, caplens=e32, payload_off=e32,
                         pending=e32, counts=[0, 0, 0, 0], datagrams=0,
-                        data=torch.empty(0, dtype=torch.uint8, device=dev))
+                        data=torch.empty(0, dtype=torch.uint8, device=dev),
+                        **(dict(pending_seen=e64, time_counts=[0, 0]) if self.timed else {}))
         rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
         lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
         flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
         st = torch.cuda.current_stream()
         self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
         groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=DEFRAG6, stream=st)
-        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, stream=st)
+        tk = dict(seen=timestamps, discard_older_than=discard_t) if self.timed else {}
+        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, stream=st, **tk)
         counts = out["counts"].cpu().tolist()
         if counts[3]:  # re-emission: the batch's size does not bound the datagrams' bytes
             out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, data_cap=counts[2],
-                                           stream=st)
+                                           stream=st, **tk)
             counts = out["counts"].cpu().tolist()
         D, K = counts[0], counts[1]
         pend = out["pending"][:K]
+        pseen = out["pending_seen"][:K] if self.timed else None
         if K and D and self.drop_completed:
             gof = groups["group_of"].long()
             done = torch.zeros(n, dtype=torch.bool, device=dev)
             done[gof.index_select(0, out["last"][:D].long())] = True
-            pend = pend[~done.index_select(0, gof.index_select(0, pend.long()))]
+            keep = ~done.index_select(0, gof.index_select(0, pend.long()))
+            pend = pend[keep]
+            if self.timed:
+                pseen = pseen[keep]
             K = int(pend.numel())
         if K:
             total = int(caplens.index_select(0, pend.long()).sum(dtype=torch.int64).item())
@@ -444,6 +570,9 @@ class IPv6Defragmenter:
             self._pending = (d2[:total], o2, c2)
         else:
             self._pending = None
+        if self.timed:
+            self._pending_seen = pseen.clone() if K else None
+            out.update(pending_seen=pseen, time_counts=out["time_counts"].cpu().tolist())
         counts[1] = K
         out.update(verdict=out["verdict"][P:], last=out["last"][:D] - P, head=out["head"][:D] - P,
                    length=out["length"][:D], offsets=out["offsets"][:D], caplens=out["caplens"][:D],
@@ -466,7 +595,8 @@ class Assembler:
     CONNECTION-grouped batch, the streams' bytes, every packet's verdict and
     the state at the end. One call behaves like a fresh NewAssembler with
     MaxBufferedPagesPerConnection = max_pages fed the batch in order, then
-    FlushAll() if `flush`. No timestamps (FlushOlderThan)."""
+    FlushAll() if `flush`. With `seen` (gpk_tcpasm_batch_timed) the connections
+    keep lastSeen and FlushWithOptions{T} can run after the batch."""
 
     def __init__(self, max_packets, device=0):
         self.h = ctypes.c_void_p()
@@ -474,7 +604,8 @@ class Assembler:
         self.max_packets = int(max_packets)
 
     def assemble(self, data, offsets, caplens, records, layouts, groups, max_pages=0, flush=False, data_cap=None,
-                 stream=None, chunk_cap=None, out_data=None, carry_code=None, carry_seq=None):
+                 stream=None, chunk_cap=None, out_data=None, carry_code=None, carry_seq=None, seen=None,
+                 flush_older=0, t=0):
         """Device tensors in: the batch, its records and layouts, and `groups`
         (Grouper.group(kind=CONNECTION) of it). Returns a dict of device tensors:
         verdict[n], stream_of[n], chunks (uint8 view of gpk_tcp_chunk[chunk_cap],
@@ -483,7 +614,12 @@ class Assembler:
         pend_pkt/pend_page[chunk_cap], counts[8] and data. chunk_cap defaults to
         n + data bytes / 1900 and data_cap to the batch's data size, which always
         suffice. carry_code (int32 bit patterns) / carry_seq (int64): the first
-        carry_code.numel() packets are carried entries."""
+        carry_code.numel() packets are carried entries. seen: int64 ns per
+        packet (for a CARRY_CONN entry the connection's lastSeen, for a
+        CARRY_PAGE entry the page's Seen); with it the result also has
+        conn_last_seen[n] (per group) and time_counts[2] (flushed, closed), and
+        flush_older = 1 (FlushWithOptions{T: t}) or 2 (CloseAll too:
+        FlushOlderThan(t)) runs after the batch."""
         import torch
         n = offsets.numel()
         dev = offsets.device
@@ -517,8 +653,21 @@ class Assembler:
             "stream_data0", "conn_seq", "conn_stream", "pend_pkt", "pend_page", "counts")], out_data.data_ptr(), ccap,
             cap)
         sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
-        _lib.check(_lib.lib().gpk_tcpasm_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
-                                               ctypes.byref(op), ctypes.byref(o), sp))
+        if seen is None:
+            if flush_older:
+                raise ValueError("flush_older needs seen")
+            _lib.check(_lib.lib().gpk_tcpasm_batch(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                   ctypes.byref(op), ctypes.byref(o), sp))
+        else:
+            if seen.dtype != i64 or seen.numel() != n:
+                raise ValueError("seen: one int64 timestamp per packet")
+            seen = seen.contiguous()
+            out["conn_last_seen"] = torch.empty(m, dtype=i64, device=dev)
+            out["time_counts"] = torch.zeros(2, dtype=i64, device=dev)
+            tm = _lib.TcpasmTime(seen.data_ptr() if n else None, int(flush_older), int(t),
+                                 out["conn_last_seen"].data_ptr(), out["time_counts"].data_ptr())
+            _lib.check(_lib.lib().gpk_tcpasm_batch_timed(self.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(g),
+                                                         ctypes.byref(op), ctypes.byref(o), ctypes.byref(tm), sp))
         out["verdict"], out["stream_of"] = out["verdict"][:n], out["stream_of"][:n]
         return out
 
@@ -542,9 +691,18 @@ class TCPAssembler:
     the calls; a source packet or call is (batch number, index), batch numbers
     counting assemble() calls from 0. max_packets bounds carried entries plus
     batch; the workspaces are rebuilt larger when open connections outgrow it.
-    No timeouts: flush_all() is FlushAll()."""
 
-    def __init__(self, ctx, parser, max_packets, max_pages=0, device=0, keys=False):
+    timed=False keeps no time: flush_all() is FlushAll(), nothing ages out.
+    timed=True: assemble() takes the packets' timestamps (int64 ns, greater than
+    INT64_MIN), every connection keeps its lastSeen and every listed page its
+    Seen on the device beside the carried entries, every chunk carries `seen`
+    (Reassembly.Seen), and flush_older_than(t) is FlushOlderThan(t). A new
+    connection starts with no lastSeen; the reference lets it inherit a closed
+    connection's through its free list (include/gpk_tcpasm.h)."""
+
+    def __init__(self, ctx, parser, max_packets, max_pages=0, device=0, keys=False, timed=False):
+        self.timed = bool(timed)
+        self._carry_seen = None  # timed: int64 per carried entry (lastSeen of a CARRY_CONN, Seen of a CARRY_PAGE)
         self.ctx, self.parser = ctx, parser
         self.max_packets, self.max_pages = int(max_packets), int(max_pages)
         self.keys = keys  # also return every new stream's key (its flows' bytes)
@@ -565,19 +723,37 @@ class TCPAssembler:
         dev = torch.device("cuda", torch.cuda.current_device()) if self._carry is None else self._carry[1].device
         e = torch.empty(0, dtype=torch.uint8, device=dev)
         return self._run(e, torch.empty(0, dtype=torch.int64, device=dev),
-                         torch.empty(0, dtype=torch.int32, device=dev), True, False)
+                         torch.empty(0, dtype=torch.int32, device=dev), True, False,
+                         torch.empty(0, dtype=torch.int64, device=dev) if self.timed else None)
 
-    def assemble(self, data, offsets, caplens):
-        """One batch (device tensors: uint8 data, int64 offsets, int32 caplens).
+    def flush_older_than(self, t, close_all=True):
+        """FlushWithOptions(FlushOptions{T: t, CloseAll: close_all}); with
+        close_all FlushOlderThan(t). t in int64 ns. A carried-only call: returns
+        assemble()'s result plus flushed and closed, the reference's two return
+        values; a flush call is ("flush", round). timed=True only."""
+        import torch
+        if not self.timed:
+            raise NotImplementedError("flush_older_than: time is out of scope unless timed=True")
+        dev = torch.device("cuda", torch.cuda.current_device()) if self._carry is None else self._carry[1].device
+        e = torch.empty(0, dtype=torch.uint8, device=dev)
+        return self._run(e, torch.empty(0, dtype=torch.int64, device=dev),
+                         torch.empty(0, dtype=torch.int32, device=dev), False, False,
+                         torch.empty(0, dtype=torch.int64, device=dev), 2 if close_all else 1, int(t))
+
+    def assemble(self, data, offsets, caplens, timestamps=None):
+        """One batch (device tensors: uint8 data, int64 offsets, int32 caplens;
+        timed: int64 ns timestamps, one per packet).
         Returns dict(verdict, stream_of (global ids, per caller's packet),
         streams: [dict(id, new, closed, chunks: [dict(src, src_off, len, skip,
         call, flags, dst)], data0, data1)], data (device), counts). src and call
         are (batch, index); a flush call is ("flush", round). With keys=True a
         new stream also has key = (net type 4 or 6, src, dst, sport, dport) as
         bytes, from its creating packet."""
-        return self._run(data, offsets, caplens, False, True)
+        if self.timed != (timestamps is not None):
+            raise ValueError("timestamps go with timed=True, and only with it")
+        return self._run(data, offsets, caplens, False, True, timestamps)
 
-    def _run(self, data, offsets, caplens, flush, count_batch):
+    def _run(self, data, offsets, caplens, flush, count_batch, timestamps=None, flush_older=0, t=0):
         import numpy as np
         import torch
         dev = offsets.device
@@ -592,6 +768,8 @@ class TCPAssembler:
             caplens = torch.cat([pc, caplens])
             code = torch.tensor(np.array(ccode, dtype=np.uint32).view(np.int32), dtype=torch.int32, device=dev)
             seq = torch.tensor(cseq, dtype=torch.int64, device=dev)
+            if self.timed:
+                timestamps = torch.cat([torch.tensor(self._carry_seen, dtype=torch.int64, device=dev), timestamps])
         else:
             cgid, corigin = [], []
         n = offsets.numel()
@@ -605,7 +783,7 @@ class TCPAssembler:
             self._batch += 1
         if n == 0:
             return dict(verdict=[], stream_of=[], streams=[], data=torch.empty(0, dtype=torch.uint8, device=dev),
-                        counts=[0] * 8)
+                        counts=[0] * 8, **(dict(flushed=0, closed=0) if self.timed else {}))
         rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
         lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
         flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
@@ -613,8 +791,10 @@ class TCPAssembler:
         self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
         groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=CONNECTION, stream=st)
         out = self.assembler.assemble(data, offsets, caplens, rec, lay, groups, max_pages=self.max_pages, flush=flush,
-                                      stream=st, carry_code=code, carry_seq=seq)
+                                      stream=st, carry_code=code, carry_seq=seq,
+                                      **(dict(seen=timestamps, flush_older=flush_older, t=t) if self.timed else {}))
         counts = out["counts"].cpu().tolist()
+        seen = timestamps.cpu().tolist() if self.timed else None
         S, C, NP = counts[0], counts[1], counts[3]
         G = int(groups["counts"][0].item())
         chunks = out["chunks"].cpu().numpy().view(_lib.TCP_CHUNK_DTYPE)[:C]
@@ -640,6 +820,9 @@ class TCPAssembler:
             ch = [dict(src=origin(int(c["src"])), src_off=int(c["src_off"]), len=int(c["len"]), skip=int(c["skip"]),
                        call=call(int(c["call"])), flags=int(c["flags"]), dst=int(c["dst"]))
                   for c in chunks[chunk0[j]:chunk0[j + 1]]]
+            if self.timed:  # Reassembly.Seen: the source packet's timestamp
+                for d, c in zip(ch, chunks[chunk0[j]:chunk0[j + 1]]):
+                    d["seen"] = seen[int(c["src"])]
             streams.append(dict(id=ids[j], new=new, first=origin(first[j]), closed=None if closed[j] == _lib.TCPASM_OPEN else call(closed[j]),
                                 chunks=ch, data0=data0[j], data1=data0[j + 1]))
         if self.keys:
@@ -660,6 +843,9 @@ class TCPAssembler:
         so = out["stream_of"][P:].cpu().tolist()
         result = dict(verdict=out["verdict"][P:].cpu().tolist(), stream_of=[ids[x] if x >= 0 else -1 for x in so],
                       streams=streams, data=out["data"], counts=counts)
+        if self.timed:
+            result["flushed"], result["closed"] = out["time_counts"].cpu().tolist()
+            last_seen = out["conn_last_seen"][:G].cpu().tolist()
         # the state for the next call: per open connection its key's first packet
         # (CARRY_CONN), then its listed pages in list order (CARRY_PAGE | page)
         conn_seq = out["conn_seq"][:G].cpu().tolist()
@@ -667,7 +853,7 @@ class TCPAssembler:
         gfirst = groups["first"][:G].cpu().tolist()
         group_of = groups["group_of"].cpu().tolist()
         pend_pkt, pend_page = out["pend_pkt"][:NP].cpu().tolist(), out["pend_page"][:NP].cpu().tolist()
-        order, ncode, nseq, ngid, norigin = [], [], [], [], []
+        order, ncode, nseq, ngid, norigin, nseen = [], [], [], [], [], []
         pages = {}
         for p, k in zip(pend_pkt, pend_page):
             pages.setdefault(group_of[p], []).append((p, k))
@@ -679,6 +865,9 @@ class TCPAssembler:
             nseq.append(conn_seq[g])
             ngid.append(ids[conn_stream[g]])
             norigin.append(origin(gfirst[g]))
+            if self.timed:
+                nseen.append(last_seen[g])
+                nseen += [seen[p] for p, _ in pages.get(g, ())]
             for p, k in pages.get(g, ()):
                 order.append(p)
                 ncode.append(_lib.TCPASM_CARRY_PAGE | k)
@@ -690,8 +879,9 @@ class TCPAssembler:
             total = int(caplens.index_select(0, ot.long()).sum(dtype=torch.int64).item())
             d2, o2, c2 = pack_batch(data, offsets, caplens, ot, total_bytes=total, stream=st)
             self._carry = (d2[:total], o2, c2, ncode, nseq, ngid, norigin)
+            self._carry_seen = nseen if self.timed else None
         else:
-            self._carry = None
+            self._carry = self._carry_seen = None
         return result
 
     def close(self):

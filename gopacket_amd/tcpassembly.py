@@ -11,10 +11,22 @@ call order, ReassemblyComplete after the call that closed the connection.
 FlushAll's callbacks come in stream order (the reference iterates a Go map
 there, so it defines no order between connections).
 
-Scope: no time. FlushOlderThan / FlushWithOptions and a non-zero
-MaxBufferedPagesTotal raise: the device path has no counterpart (see the
-header). Reassembly.Seen is the caller's timestamp of the chunk's source
-packet. There is no CPU fallback.
+Time is opt-in at construction. NewAssembler(pool) keeps none: FlushOlderThan
+and FlushWithOptions raise, and Reassembly.Seen is whatever the caller passed
+as the source packet's timestamp. NewAssembler(pool, timed=True) requires
+timestamps with every batch, as an int64 array of nanoseconds
+(time.Time.UnixNano(), greater than INT64_MIN) or a _lib.CAPINFO_DTYPE array;
+the device then keeps every connection's lastSeen and every page's Seen
+(include/gpk_tcpasm.h), Reassembly.Seen is the source packet's timestamp in
+ns, and FlushOlderThan(t) / FlushWithOptions(FlushOptions(T, CloseAll)) replay
+their callbacks in stream order, as FlushAll does, and return
+(flushed, closed). One departure from the reference, documented in the header:
+a new connection starts with no lastSeen, where the reference lets it inherit
+that of the closed connection whose struct it reuses; the two agree whenever
+timestamps do not run backwards.
+
+Still out of scope: a non-zero MaxBufferedPagesTotal raises. There is no CPU
+fallback.
 """
 import numpy as np
 
@@ -23,8 +35,8 @@ from . import _lib, flows, gopacket, layers
 # the decoders of examples/statsassembly (main.go:141-142)
 DECODERS = (_lib.DEC_ETHERNET, _lib.DEC_DOT1Q, _lib.DEC_IPV4, _lib.DEC_IPV6, _lib.DEC_IPV6_EXT, _lib.DEC_TCP,
             _lib.DEC_PAYLOAD)
-SCOPE = ("%s is out of scope: the device reassembly keeps no time (include/gpk_tcpasm.h); "
-         "use FlushAll, or close old connections from Reassembly.Seen")
+SCOPE = ("%s is out of scope: this Assembler keeps no time (NewAssembler(pool, timed=True) does, "
+         "include/gpk_tcpasm.h); use FlushAll, or close old connections from Reassembly.Seen")
 
 
 class Reassembly:
@@ -36,6 +48,14 @@ class Reassembly:
 
     def __repr__(self):
         return "Reassembly(%d bytes, Skip=%d, Start=%s, End=%s)" % (len(self.Bytes), self.Skip, self.Start, self.End)
+
+
+class FlushOptions:
+    """assembly.go:207-210. T in int64 ns."""
+    __slots__ = ("T", "CloseAll")
+
+    def __init__(self, T=_lib.TIME_ZERO, CloseAll=False):
+        self.T, self.CloseAll = T, CloseAll
 
 
 class Stream:
@@ -70,8 +90,9 @@ def NewStreamPool(factory):
 class Assembler:
     """NewAssembler(pool) (:477-486) for batches."""
 
-    def __init__(self, pool, ctx=None, parser=None, max_packets=1 << 20, device=0):
+    def __init__(self, pool, ctx=None, parser=None, max_packets=1 << 20, device=0, timed=False):
         self.connPool = pool
+        self.timed = bool(timed)
         self.MaxBufferedPagesPerConnection = 0
         self.MaxBufferedPagesTotal = 0
         self._args = (ctx, parser, int(max_packets), device)
@@ -87,33 +108,53 @@ class Assembler:
             ctx, parser, n, device = self._args
             ctx = ctx or engine.Context(device)
             parser = parser or engine.ParserConfig(int(layers.LayerTypeEthernet), list(DECODERS))
-            self._dev = flows.TCPAssembler(ctx, parser, n, device=device, keys=True)
+            self._dev = flows.TCPAssembler(ctx, parser, n, device=device, keys=True, timed=self.timed)
         self._dev.max_pages = int(self.MaxBufferedPagesPerConnection)
         return self._dev
 
     def AssembleBatch(self, data, offsets, caplens, timestamps=None):
         """AssembleWithTimestamp (:536) for every packet of a batch, in order.
         data/offsets/caplens: numpy arrays (uint8, offsets, lengths) or device
-        tensors; timestamps: one value per packet, handed back as Seen."""
+        tensors; timestamps: one value per packet, handed back as Seen; timed: an
+        int64 ns array or a _lib.CAPINFO_DTYPE array, required."""
         import torch
         dev = self._device()
+        ns = None
+        if self.timed:
+            if timestamps is None:
+                raise ValueError("a timed Assembler needs the packets' timestamps")
+            ts = np.asarray(timestamps)
+            if ts.dtype == _lib.CAPINFO_DTYPE:
+                ts = ts["ts_sec"].astype(np.int64) * 1000000000 + ts["ts_nsec"].astype(np.int64)
+            elif ts.dtype != np.int64:
+                raise ValueError("timestamps: int64 nanoseconds or a CAPINFO_DTYPE array")
+            timestamps = ts.tolist()
+            ns = torch.from_numpy(np.ascontiguousarray(ts)).cuda()
         if not torch.is_tensor(data):
             data = torch.from_numpy(np.concatenate([np.asarray(data, np.uint8), np.zeros(16, np.uint8)])).cuda()
             offsets = torch.from_numpy(np.asarray(offsets).astype(np.int64)).cuda()
             caplens = torch.from_numpy(np.asarray(caplens).astype(np.int32)).cuda()
         bno = dev._batch
         self._seen[bno] = timestamps
-        self._replay(dev.assemble(data, offsets, caplens))
+        self._replay(dev.assemble(data, offsets, caplens, ns) if self.timed else dev.assemble(data, offsets, caplens))
 
     def FlushAll(self):
         """:279-290 -> the number of connections closed"""
         return self._replay(self._device().flush_all())
 
     def FlushOlderThan(self, t):
-        raise NotImplementedError(SCOPE % "FlushOlderThan")
+        """:272-274 -> (flushed, closed); t in int64 ns. timed=True only."""
+        if not self.timed:
+            raise NotImplementedError(SCOPE % "FlushOlderThan")
+        return self.FlushWithOptions(FlushOptions(T=t, CloseAll=True))
 
     def FlushWithOptions(self, opt):
-        raise NotImplementedError(SCOPE % "FlushWithOptions")
+        """:238-269 -> (flushed, closed). timed=True only."""
+        if not self.timed:
+            raise NotImplementedError(SCOPE % "FlushWithOptions")
+        res = self._device().flush_older_than(int(opt.T), close_all=bool(opt.CloseAll))
+        self._replay(res)
+        return res["flushed"], res["closed"]
 
     def _replay(self, res):
         # one host copy of the streams' bytes; every Reassembly.Bytes is a view of it

@@ -33,8 +33,17 @@
  * Harness rule (as in gpk_flows.h): "the IPv4" of a packet is its layout
  * slot's last IPv4, the one the grouping keyed.
  *
- * Out of scope: timeouts. DiscardOlderThan and LastSeen have no counterpart; a
- * caller that wants them drops pending fragments itself.
+ * Time (gpk_defrag_batch_timed): fragmentList.LastSeen and DiscardOlderThan
+ * (:138-149). Timestamps are int64 nanoseconds (time.Time.UnixNano()), Before
+ * is <.
+ *   LastSeen = t (:249) is an assignment made by every call that passes the
+ *       duplicate check: "counted, not listed" fragments and fragments whose
+ *       build then fails stamp too; an ignored duplicate (:223-238) returns
+ *       before it, and calls that fail the security checks never reach insert.
+ *       `pending` lists exactly those stamping fragments of the live keys in
+ *       arrival order, so a key's LastSeen is seen[] of its last pending packet.
+ *   DiscardOlderThan(t) after the batch: keys with LastSeen < t leave pending.
+ * gpk_defrag_batch itself keeps no time.
  *
  * Cost: the list walk of one key is done by one wave (64 list entries per
  * step); build is sequential in list order, so a key that re-builds on every
@@ -115,6 +124,24 @@ typedef struct gpk_datagrams {
  * decode with layouts) are device-resident. Asynchronous on `stream`. */
 int gpk_defrag_batch(gpk_defragger* d, const gpk_batch* batch, const gpk_results* res, const gpk_groups* groups,
                      const gpk_datagrams* out, void* stream);
+
+/* Time for gpk_defrag_batch_timed: device arrays, n = batch size. A live key
+ * has been stamped at least once, so Go's zero time.Time never shows. */
+typedef struct gpk_defrag_time {
+  const int64_t* seen;   /* [n]  packet i's DefragIPv4WithTimestamp timestamp; for a fragment
+                                 carried over from an earlier batch its key's LastSeen
+                                 (pending_seen of that batch), which replays to the same state */
+  uint32_t discard;      /*      != 0: DiscardOlderThan(t) runs after the batch                  */
+  int64_t t;
+  int64_t* pending_seen; /* [n]  out: LastSeen of pending[k]'s key                               */
+  uint64_t* counts;      /* [2]  out: keys discarded (the reference's return value), packets
+                                 dropped with them                                               */
+} gpk_defrag_time;
+
+/* gpk_defrag_batch, then the time operations: out->pending and out->counts[1]
+ * hold the survivors of the discard. Everything else is gpk_defrag_batch's. */
+int gpk_defrag_batch_timed(gpk_defragger* d, const gpk_batch* batch, const gpk_results* res, const gpk_groups* groups,
+                           const gpk_datagrams* out, const gpk_defrag_time* tm, void* stream);
 
 #ifdef __cplusplus
 }

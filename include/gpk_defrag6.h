@@ -57,9 +57,25 @@
  *   - the example's "ignore unless UDP or TCP" filter is the caller's and is
  *     not applied.
  *
- * Out of scope: time. DiscardOlderThan has no counterpart; since the reference
- * removes nothing otherwise, a caller that wants state to shrink drops pending
- * packets itself (gopacket_amd.flows.IPv6Defragmenter: flush, drop_completed).
+ * Time (gpk_defrag6_batch_timed): the entry's time and DiscardOlderThan
+ * (:183-194). Timestamps are int64 nanoseconds (time.Time.UnixNano()), Before
+ * is <.
+ *   - the deferred d.container[fg.Identification].time = time.Now() (:84-87)
+ *     runs after EVERY call on the Identification and stamps the key's head
+ *     entry as it is then: the first call, ignored duplicates and calls that
+ *     return a datagram included. DiscardOlderThan reads the head entry's time
+ *     too, and a head replaced by an insert in front of it is stamped by that
+ *     very call, so a key's time is the timestamp of its last call.
+ *   - scope decision: the reference has no timestamp parameter here and reads
+ *     the wall clock. The caller's timestamp plays time.Now(), as
+ *     DefragIPv4WithTimestamp's does for IPv4.
+ *   - `carry` packets stamp too; their seen[] is the carried key time, so a
+ *     replay reproduces it even when the last stamper was an unlisted duplicate.
+ *   - DiscardOlderThan(t) after the batch: keys with time < t leave pending.
+ * gpk_defrag6_batch itself keeps no time; without a discard the reference
+ * removes nothing, and a caller that wants state to shrink otherwise drops
+ * pending packets itself (gopacket_amd.flows.IPv6Defragmenter: flush,
+ * drop_completed).
  *
  * Cost: one wave per key walks its packets; a lookup or insert touches the list
  * 64 entries at a time. The position of the first stop of the head's chain is
@@ -145,6 +161,25 @@ typedef struct gpk_datagrams6 {
  * datagrams a second time). Asynchronous on `stream`. */
 int gpk_defrag6_batch(gpk_defragger6* d, const gpk_batch* batch, const gpk_results* res, const gpk_groups* groups,
                       uint64_t carry, const gpk_datagrams6* out, void* stream);
+
+/* Time for gpk_defrag6_batch_timed: device arrays, n = batch size. Every key
+ * has been stamped by its first call, so Go's zero time.Time never shows. */
+typedef struct gpk_defrag6_time {
+  const int64_t* seen;   /* [n]  the timestamp of packet i's call; for a `carry` packet its key's
+                                 time (pending_seen of the batch it comes from)                  */
+  uint32_t discard;      /*      != 0: DiscardOlderThan(t) runs after the batch                  */
+  int64_t t;
+  int64_t* pending_seen; /* [n]  out: the time of pending[k]'s key                               */
+  uint64_t* counts;      /* [2]  out: keys discarded (the reference's return value), listed
+                                 fragments dropped with them                                     */
+} gpk_defrag6_time;
+
+/* gpk_defrag6_batch, then the time operations: out->pending and
+ * out->counts[1] hold the survivors of the discard. Everything else is
+ * gpk_defrag6_batch's. */
+int gpk_defrag6_batch_timed(gpk_defragger6* d, const gpk_batch* batch, const gpk_results* res,
+                            const gpk_groups* groups, uint64_t carry, const gpk_datagrams6* out,
+                            const gpk_defrag6_time* tm, void* stream);
 
 #ifdef __cplusplus
 }

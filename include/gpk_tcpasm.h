@@ -46,10 +46,35 @@
  * (layout.end[TCP] - start) - DataOffset*4 bytes after the header (none where
  * the header claims more than the slice holds).
  *
- * Out of scope: time. Seen, lastSeen, FlushOlderThan and FlushWithOptions{T}
- * have no counterpart: a chunk names its source packet, so a caller reads Seen
- * from its own capture info and closes old connections itself.
- * MaxBufferedPagesTotal is 0 always.
+ * Time (gpk_tcpasm_batch_timed): lastSeen, page.Seen and FlushWithOptions{T}
+ * (FlushOlderThan). Timestamps are int64 nanoseconds (time.Time.UnixNano()),
+ * Before is <; Go's zero time.Time (a fresh lastSeen) is INT64_MIN, so callers'
+ * timestamps must be greater than INT64_MIN.
+ *   lastSeen (:567-569)  every call that gets a connection does
+ *       if lastSeen.Before(ts) lastSeen = ts: a maximum, not the last value.
+ *       "Useless" packets (:538) and GPK_TCPASM_NOCONN calls never reach it.
+ *   A connection created in the batch starts from INT64_MIN. SCOPE DECISION that
+ *       departs from the reference: connection.reset (:388-396) does not clear
+ *       lastSeen and StreamPool recycles connection structs from a LIFO free
+ *       list (:479-493, :662-667), so in the reference a new connection inherits
+ *       the lastSeen of whatever closed connection last used its struct: a
+ *       serial dependency across all keys. It shows only when timestamps run
+ *       backwards (a new connection's first packet otherwise overwrites it).
+ *       The device starts every new connection fresh.
+ *   page.Seen  the timestamp of the page's source packet; all pages of one
+ *       packet share it. Reassembly.Seen of a chunk is seen[chunk.src].
+ *   FlushWithOptions (:238-269) after the batch, per open connection: while the
+ *       list is not empty and the FIRST page's Seen < T, skipFlush (round r is
+ *       call GPK_TCPASM_CALL_FLUSH | r) — the contiguous pages behind that page
+ *       go out whatever their age, and a young first page shields older pages
+ *       behind it; a send whose last chunk has End closes the connection and
+ *       ends the loop. With CloseAll a connection still open with an empty list
+ *       and lastSeen < T is closed (call CALL_FLUSH | r). The reference visits
+ *       the connections in a Go map's order, which is undefined: outputs stay
+ *       stream-major.
+ * gpk_tcpasm_batch itself keeps no time: a chunk names its source packet, so a
+ * caller reads Seen from its own capture info. MaxBufferedPagesTotal is 0
+ * always.
  *
  * Cost: one wave walks one key. In-order runs retire 64 packets per step; a
  * queued packet costs one back-scan of the key's page list (64 entries per
@@ -180,6 +205,25 @@ typedef struct gpk_tcp_streams {
  * grouping of this batch) are device-resident. Asynchronous on `stream`. */
 int gpk_tcpasm_batch(gpk_tcpasm* a, const gpk_batch* batch, const gpk_results* res, const gpk_groups* groups,
                      const gpk_tcpasm_opts* opts, const gpk_tcp_streams* out, void* stream);
+
+/* Time for gpk_tcpasm_batch_timed. */
+typedef struct gpk_tcpasm_time {
+  const int64_t* seen;     /* [n] device: packet i's AssembleWithTimestamp timestamp; for a CARRY_CONN
+                              entry the connection's lastSeen, for a CARRY_PAGE entry that page's Seen */
+  uint32_t flush_older;    /* after the batch: 0 nothing, 1 FlushWithOptions{T}, 2 FlushWithOptions{T, CloseAll}
+                              (= FlushOlderThan(T)); together with opts.flush: an argument error */
+  int64_t t;
+  int64_t* conn_last_seen; /* [n] out, per group: lastSeen of the connection open at the end
+                              (INT64_MIN where none is)                                            */
+  uint64_t* counts;        /* [2] out: flushed, closed: FlushWithOptions' two return values        */
+} gpk_tcpasm_time;
+
+/* gpk_tcpasm_batch with time. conn_last_seen[g] and seen[] of the pending
+ * pages' packets, fed back as the seen[] of the next batch's carried entries,
+ * reproduce the reference's state. */
+int gpk_tcpasm_batch_timed(gpk_tcpasm* a, const gpk_batch* batch, const gpk_results* res, const gpk_groups* groups,
+                           const gpk_tcpasm_opts* opts, const gpk_tcp_streams* out, const gpk_tcpasm_time* tm,
+                           void* stream);
 
 #ifdef __cplusplus
 }

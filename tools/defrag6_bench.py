@@ -17,7 +17,10 @@ copy_kernel on the equivalent IPv4 batch, gpk_pack_batch's byte kernel moving
 the keyed packets of the IPv6 batch, and a device-to-device memcpy of the
 mover's byte count (the ceiling, not a target). Kernel times come from the
 profiler's device timeline, one sample per run; medians and min..max over
---runs timed runs after --warmup.
+--runs timed runs after --warmup. A `timed` row follows
+(tools/reasm_time_ab.py): gpk_defrag6_batch and gpk_defrag6_batch_timed
+(timestamps in, key times out, no discard) on the same batch, interleaved, with
+the ratio of their plan times.
 
   python tools/defrag6_bench.py --out profiles/defrag6.json
 """
@@ -216,6 +219,17 @@ def main():
         res["kernel_names_seen"] = sorted(kern)[:40]
     res["memcpy_GBps"] = spread([src_len / (x * 1e6) for x in t["memcpy"]])
     res["datagrams_per_s"] = counts[0] / (statistics.median(t["end_to_end"]) / 1e3)
+    import reasm_time_ab
+    seen = torch.arange(b6["n"], dtype=torch.int64, device="cuda") * 1000 + 1700000000 * 10 ** 9
+
+    def call(**kw):
+        return df6.defrag(b6["d"], b6["o"], b6["c"], b6["rec"], b6["lay"], groups, out_data=out6, data_cap=need,
+                          stream=st, **kw)
+
+    res["timed"] = reasm_time_ab.ab_rows(torch, profile, [ProfilerActivity.CPU, ProfilerActivity.CUDA], call,
+                                         lambda: call(seen=seen), a.runs, a.warmup,
+                                         shared=("prep6_kernel", "plan6_kernel"),
+                                         timed_only=("key6_kernel", "drop6_kernel", "seen6_kernel"))
     line = json.dumps(res)
     print(line)
     if a.out:

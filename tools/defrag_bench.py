@@ -16,6 +16,9 @@ gpk_pack_batch's byte kernel moving the keyed packets of the same batch, and a
 device-to-device memcpy of the copy's byte count (the ceiling, not a target).
 Kernel times come from the profiler's device timeline, one sample per run;
 medians and min..max over --runs timed runs after --warmup.
+A `timed` row follows (tools/reasm_time_ab.py): gpk_defrag_batch and
+gpk_defrag_batch_timed (timestamps in, LastSeen out, no discard) on the same
+batch, interleaved, with the ratio of their plan times.
 
   python tools/defrag_bench.py --out profiles/defrag.json
 """
@@ -170,6 +173,16 @@ def main():
         res["kernel_names_seen"] = sorted(kern)[:40]
     res["memcpy_GBps"] = spread([copy_bytes / (x * 1e6) for x in t["memcpy"]])
     res["datagrams_per_s"] = counts[0] / (statistics.median(t["end_to_end"]) / 1e3)
+    import reasm_time_ab
+    seen = torch.arange(n, dtype=torch.int64, device="cuda") * 1000 + 1700000000 * 10 ** 9
+
+    def call(**kw):
+        return df.defrag(d, o, c, rec, lay, groups, out_data=out_data, data_cap=d.numel(), stream=st, **kw)
+
+    res["timed"] = reasm_time_ab.ab_rows(torch, profile, [ProfilerActivity.CPU, ProfilerActivity.CUDA], call,
+                                         lambda: call(seen=seen), a.runs, a.warmup,
+                                         shared=("prep_kernel", "plan_kernel"),
+                                         timed_only=("mark_kernel", "key_kernel", "drop_kernel", "seen_kernel"))
     line = json.dumps(res)
     print(line)
     if a.out:

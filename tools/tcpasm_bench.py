@@ -17,6 +17,9 @@
     segment is queued and popped by the next: one packet per step).
 Kernel times come from the profiler's device timeline, one sample per run;
 medians and min..max over --runs timed runs after --warmup.
+Every batch also gets a `timed` row (tools/reasm_time_ab.py): gpk_tcpasm_batch
+and gpk_tcpasm_batch_timed (timestamps in, lastSeen kept, no FlushOlderThan) on
+the same batch, interleaved, with the ratio of their plan times.
 
   python tools/tcpasm_bench.py --out profiles/tcpasm.json
 """
@@ -159,6 +162,19 @@ def measure(torch, profile, activities, ctx, parser, flows, batch, a, memcpy):
     if memcpy:
         res["memcpy_GBps"] = spread([nbytes / (x * 1e6) for x in t["memcpy"]])
     res["packets_per_s"] = n / (statistics.median(t["end_to_end"]) / 1e3)
+    import reasm_time_ab
+    seen = torch.arange(n, dtype=torch.int64, device="cuda") * 1000 + 1700000000 * 10 ** 9
+
+    def call(**kw):
+        return asm.assemble(d, o, c, rec, lay, groups, max_pages=a.max_pages, flush=True, out_data=out_data,
+                            data_cap=d.numel(), stream=st, **kw)
+
+    res["timed"] = reasm_time_ab.ab_rows(torch, profile, activities, call, lambda: call(seen=seen), a.runs, a.warmup,
+                                         shared=("prep_kernel",),
+                                         untimed_only=("plan_kernel<true, false>", "plan_kernel<false, false>",
+                                                       "plan_kernelILb1ELb0E", "plan_kernelILb0ELb0E"),
+                                         timed_only=("plan_kernel<true, true>", "plan_kernel<false, true>",
+                                                     "plan_kernelILb1ELb1E", "plan_kernelILb0ELb1E"))
     g.close()
     asm.close()
     return res
