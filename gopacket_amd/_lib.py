@@ -131,6 +131,11 @@ class Groups(ctypes.Structure):
     _fields_ = [("group_of", ctypes.c_void_p), ("perm", ctypes.c_void_p), ("start", ctypes.c_void_p),
                 ("first", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
 
+    @classmethod
+    def of(cls, groups):
+        """From Grouper.group's dict of device tensors."""
+        return cls(*[groups[k].data_ptr() for k in ("group_of", "perm", "start", "first", "counts")])
+
 
 # include/gpk_defrag.h constants
 DEFRAG_HELD, DEFRAG_EHOLE, DEFRAG_EINVALID, DEFRAG_EMAXLEN, DEFRAG_EPANIC = -16, -17, -18, -19, -20
@@ -380,6 +385,11 @@ class Batch(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("offsets", ctypes.c_void_p), ("caplens", ctypes.c_void_p),
                 ("n", ctypes.c_uint64), ("data_bytes", ctypes.c_uint64)]
 
+    @classmethod
+    def of(cls, data, offsets, caplens):
+        """From the three device tensors of a batch."""
+        return cls(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), offsets.numel(), data.numel())
+
 
 class Results(ctypes.Structure):
     _fields_ = [("records", ctypes.c_void_p), ("err_args", ctypes.c_void_p), ("flows", ctypes.c_void_p),
@@ -577,6 +587,11 @@ def check(rc):
         L = lib()
         raise GpkError("gpk: %s (%d) %s" % (L.gpk_strerror(rc).decode(), rc, L.gpk_last_hip_error().decode()))
     return rc
+
+
+def stream_ptr(stream):
+    """A raw hipStream_t from a torch stream, an int handle or None."""
+    return None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
 
 
 class _Mem:

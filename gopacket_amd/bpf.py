@@ -56,7 +56,7 @@ class BPF:
         if ret is None:
             ret = torch.empty(n, dtype=torch.int32, device=offsets.device)
         b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         _lib.check(_lib.lib().gpk_bpf_run(self.h, ctypes.byref(b), wirelens.data_ptr() if wirelens is not None
                                           else None, ret.data_ptr(), sp))
         return ret
@@ -71,7 +71,7 @@ class BPF:
         oi = torch.empty(max(n, 1), dtype=torch.int32, device=dev)
         cnt = torch.zeros(1, dtype=torch.int32, device=dev)
         b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         _lib.check(_lib.lib().gpk_bpf_select(self.h, ctypes.byref(b), wirelens.data_ptr() if wirelens is not None
                                              else None, oo.data_ptr(), oc.data_ptr(), oi.data_ptr(), cnt.data_ptr(),
                                              sp))

@@ -9,7 +9,7 @@
 //   3. counts_kernel  blocks written, bytes needed, packets in error, overflow
 //   4. frame_kernel   one group of G lanes per output packet, G = 64 (one wave)
 //                     or 16 (four packets per wave, for batches of small
-//                     blocks). The data moves as in gpk_defrag.hip's copy_bytes:
+//                     blocks). The data moves with gpk_copy.h's copy_bytes<G>:
 //                     destination-aligned 16-byte stores, the source realigned
 //                     from two aligned 16-byte loads, a byte head and tail. The
 //                     64-lane form switches on the source's dword phase, which
@@ -32,7 +32,9 @@
 #include <new>
 
 #include "../../include/gpk_capwrite.h"
+#include "gpk_copy.h"
 #include "gpk_devguard.h"
+#include "gpk_scan.h"
 
 namespace {
 
@@ -119,9 +121,6 @@ __global__ void __launch_bounds__(256) size_kernel(SizeArgs a) {
   a.bsize[j] = size;
 }
 
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
 using SizeIt = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
 
 __global__ void __launch_bounds__(256) counts_kernel(const int32_t* status, const uint64_t* block_off, uint64_t m,
@@ -145,78 +144,6 @@ __global__ void __launch_bounds__(256) counts_kernel(const int32_t* status, cons
   if ((threadIdx.x & 63) == 0) {
     if (wrote) atomicAdd((unsigned long long*)&counts[0], (unsigned long long)wrote);
     if (errors) atomicAdd((unsigned long long*)&counts[2], (unsigned long long)errors);
-  }
-}
-
-// ---- the byte mover: gpk_defrag.hip's copy_vectors / copy_bytes for a group
-// of G lanes. Every 16-byte load is aligned and holds at least one byte of the
-// source, so it stays inside the pages the source is in.
-template <int Q>
-__device__ __forceinline__ void copy_vectors(uint4* d, const uint4* sa, uint32_t nvec, uint32_t r, uint32_t lane) {
-  for (uint32_t v = lane; v < nvec; v += 64) {
-    const uint4 A = sa[v], B = sa[v + 1];
-    const uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
-    uint4 out;
-    out.x = (uint32_t)((((uint64_t)w[Q + 1] << 32) | w[Q]) >> r);
-    out.y = (uint32_t)((((uint64_t)w[Q + 2] << 32) | w[Q + 1]) >> r);
-    out.z = (uint32_t)((((uint64_t)w[Q + 3] << 32) | w[Q + 2]) >> r);
-    out.w = (uint32_t)((((uint64_t)w[Q + 4] << 32) | w[Q + 3]) >> r);
-    d[v] = out;
-  }
-}
-
-__device__ __forceinline__ uint32_t pick4(uint32_t q, uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return q == 0 ? a : q == 1 ? b : q == 2 ? c : d;
-}
-
-// 16 lanes, the phase a per-lane value: the five words are selected
-__device__ __forceinline__ void copy_vectors_sel(uint4* d, const uint4* sa, uint32_t nvec, uint32_t sh, uint32_t lane) {
-  const uint32_t q = sh >> 2, r = (sh & 3) * 8;
-  for (uint32_t v = lane; v < nvec; v += 16) {
-    const uint4 A = sa[v];
-    uint4 B = A;
-    if (sh) B = sa[v + 1];  // an aligned source has no byte in the next word
-    const uint32_t w0 = pick4(q, A.x, A.y, A.z, A.w), w1 = pick4(q, A.y, A.z, A.w, B.x),
-                   w2 = pick4(q, A.z, A.w, B.x, B.y), w3 = pick4(q, A.w, B.x, B.y, B.z),
-                   w4 = pick4(q, B.x, B.y, B.z, B.w);
-    uint4 out;
-    out.x = (uint32_t)((((uint64_t)w1 << 32) | w0) >> r);
-    out.y = (uint32_t)((((uint64_t)w2 << 32) | w1) >> r);
-    out.z = (uint32_t)((((uint64_t)w3 << 32) | w2) >> r);
-    out.w = (uint32_t)((((uint64_t)w4 << 32) | w3) >> r);
-    d[v] = out;
-  }
-}
-
-template <int G>
-__device__ __forceinline__ void copy_bytes(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-  uint32_t head = (uint32_t)(-(uintptr_t)dst & 15);
-  if (head > n) head = n;
-  const uint32_t body = n - head, nvec = body >> 4, tail = body & 15;
-  uint8_t* d16 = dst + head;
-  const uint8_t* s16 = src + head;
-  constexpr uint32_t kTailLane = G == 64 ? 16 : 0;  // head and tail are at most 15 bytes each
-  if (lane < head) dst[lane] = src[lane];
-  if (lane >= kTailLane && lane < kTailLane + tail)
-    d16[nvec * 16 + lane - kTailLane] = s16[nvec * 16 + lane - kTailLane];
-  if (!nvec) return;
-  const uint32_t sh = (uint32_t)((uintptr_t)s16 & 15);
-  const uint4* sa = (const uint4*)(s16 - sh);
-  uint4* d = (uint4*)d16;
-  if (G == 16) {
-    copy_vectors_sel(d, sa, nvec, sh, lane);
-    return;
-  }
-  if (sh == 0) {
-    for (uint32_t v = lane; v < nvec; v += 64) d[v] = sa[v];
-    return;
-  }
-  const uint32_t r = (sh & 3) * 8;
-  switch (sh >> 2) {  // wave-uniform: one packet per wave
-    case 0: copy_vectors<0>(d, sa, nvec, r, lane); break;
-    case 1: copy_vectors<1>(d, sa, nvec, r, lane); break;
-    case 2: copy_vectors<2>(d, sa, nvec, r, lane); break;
-    default: copy_vectors<3>(d, sa, nvec, r, lane); break;
   }
 }
 
@@ -258,14 +185,14 @@ __global__ void __launch_bounds__(256) frame_kernel(FrameArgs a) {
     } else {
       for (uint32_t b = lane; b < hbytes; b += G) dst[b] = (uint8_t)(head_word(h, b >> 2) >> ((b & 3) * 8));
     }
-    copy_bytes<G>(dst + hbytes, a.data + a.offsets[i], caplen, lane);
+    gpk::copy_bytes<G>(dst + hbytes, a.data + a.offsets[i], caplen, lane);
     if (!ng) continue;
     const uint32_t pad = (4 - (caplen & 3)) & 3;
     uint8_t* t = dst + kNgHead + caplen;
     if (lane < pad) t[lane] = 0;
     t += pad;
     const uint32_t optlen = size - kNgHead - caplen - pad - 4;
-    if (optlen) copy_bytes<G>(t, a.opt_data + a.opt_off[j], optlen, lane);
+    if (optlen) gpk::copy_bytes<G>(t, a.opt_data + a.opt_off[j], optlen, lane);
     t += optlen;
     if (((uintptr_t)t & 3) == 0) {
       if (lane == 0) *(uint32_t*)t = size;

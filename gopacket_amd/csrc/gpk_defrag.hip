@@ -44,7 +44,8 @@
 
 #include "../../include/gpk_defrag.h"
 #include "gpk_copy.h"
-#include "gpk_devguard.h"
+#include "gpk_scan.h"
+#include "gpk_workspace.h"
 
 namespace {
 
@@ -270,12 +271,6 @@ __global__ void __launch_bounds__(64) plan_kernel(PlanArgs a) {
   }
 }
 
-struct NonZero {
-  __host__ __device__ uint32_t operator()(uint32_t v) const { return v != 0; }
-};
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
 struct IsPending {  // counted for the instance of its key that is still open at the end of the batch
   const uint32_t* inst;
   const uint32_t* final_inst;
@@ -436,26 +431,26 @@ struct gpk_defragger {
   uint64_t cap = 0;
   Work w{};
   TimeWork tw{};
-  void* tmp = nullptr;
+  uint8_t* tmp = nullptr;
   size_t tmp_bytes = 0;
+  gpk::Workspace ws;
 };
 
 namespace {
 
-void free_all(gpk_defragger* d) {
-  for (void* p : {(void*)d->w.info, (void*)d->w.inst, (void*)d->w.final_inst, (void*)d->w.dsize, (void*)d->w.dhigh,
-                  (void*)d->w.dnum, (void*)d->w.ddst, (void*)d->w.ppos, (void*)d->w.seg_pkt, (void*)d->w.seg_skip,
-                  (void*)d->w.seg_dst, (void*)d->w.seg_owner, (void*)d->tw.key_last, (void*)d->tw.key_cnt,
-                  (void*)d->tw.key_seen, (void*)d->tw.dead, d->tmp})
-    if (p) (void)hipFree(p);
+void carve(gpk_defragger* d) {  // every device array of the handle
+  const uint64_t n = d->cap;
+  d->ws.take(d->w.info, n), d->ws.take(d->w.inst, n), d->ws.take(d->w.final_inst, n), d->ws.take(d->w.dsize, n);
+  d->ws.take(d->w.dhigh, n), d->ws.take(d->w.dnum, n), d->ws.take(d->w.ddst, n), d->ws.take(d->w.ppos, n);
+  d->ws.take(d->w.seg_pkt, n), d->ws.take(d->w.seg_skip, n), d->ws.take(d->w.seg_dst, n);
+  d->ws.take(d->w.seg_owner, n), d->ws.take(d->tw.key_last, n), d->ws.take(d->tw.key_cnt, n);
+  d->ws.take(d->tw.key_seen, n), d->ws.take(d->tw.dead, n), d->ws.take(d->tmp, d->tmp_bytes);
 }
 
 }  // namespace
 
 extern "C" int gpk_defragger_create(gpk_defragger** out, int device, uint64_t max_packets) {
-  if (!out || max_packets == 0 || max_packets >= (1ull << 28)) return GPK_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GPK_ENODEV;
+  if (const int rc = gpk::check_create(out, device, max_packets)) return rc;
   gpk::DeviceScope dscope(device);  // the caller's device is restored on return
   if (dscope.err != hipSuccess) return GPK_EHIP;
   gpk_defragger* d = new (std::nothrow) gpk_defragger();
@@ -471,23 +466,13 @@ extern "C" int gpk_defragger_create(gpk_defragger** out, int device, uint64_t ma
             hipcub::DeviceScan::ExclusiveSum(
                 nullptr, b2, PendIt(hipcub::CountingInputIterator<uint32_t>(0), IsPending{nullptr, nullptr, nullptr}),
                 (uint32_t*)nullptr, (int)n) == hipSuccess;
-  d->tmp_bytes = std::max(std::max(b0, b1), std::max(b2, (size_t)16));
-  Work& w = d->w;
-  ok = ok && hipMalloc((void**)&w.info, n * 16) == hipSuccess && hipMalloc((void**)&w.inst, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.final_inst, n * 4) == hipSuccess && hipMalloc((void**)&w.dsize, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.dhigh, n * 4) == hipSuccess && hipMalloc((void**)&w.dnum, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.ddst, n * 8) == hipSuccess && hipMalloc((void**)&w.ppos, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.seg_pkt, n * 4) == hipSuccess && hipMalloc((void**)&w.seg_skip, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.seg_dst, n * 4) == hipSuccess && hipMalloc((void**)&w.seg_owner, n * 4) == hipSuccess &&
-       hipMalloc((void**)&d->tw.key_last, n * 4) == hipSuccess &&
-       hipMalloc((void**)&d->tw.key_cnt, n * 4) == hipSuccess &&
-       hipMalloc((void**)&d->tw.key_seen, n * 8) == hipSuccess && hipMalloc((void**)&d->tw.dead, n * 4) == hipSuccess &&
-       hipMalloc(&d->tmp, d->tmp_bytes) == hipSuccess;
-  if (!ok) {
-    free_all(d);
+  d->tmp_bytes = gpk::max_temp({b0, b1, b2});
+  carve(d);
+  if (!ok || !d->ws.alloc()) {
     delete d;
     return GPK_ENOMEM;
   }
+  carve(d);
   *out = d;
   return GPK_OK;
 }
@@ -496,7 +481,7 @@ extern "C" int gpk_defragger_destroy(gpk_defragger* d) {
   if (!d) return GPK_EINVAL;
   gpk::DeviceScope dscope(d->device);
   (void)hipDeviceSynchronize();
-  free_all(d);
+  d->ws.release();
   delete d;
   return GPK_OK;
 }

@@ -51,8 +51,9 @@
 
 #include "../../include/gpk_defrag6.h"
 #include "gpk_copy.h"
-#include "gpk_devguard.h"
 #include "gpk_frag6.h"
+#include "gpk_scan.h"
+#include "gpk_workspace.h"
 
 namespace {
 
@@ -236,12 +237,6 @@ __global__ void __launch_bounds__(64) plan6_kernel(PlanArgs a) {
   }
 }
 
-struct NonZero {
-  __host__ __device__ uint32_t operator()(uint32_t v) const { return v != 0; }
-};
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
-};
 using DnumIt = hipcub::TransformInputIterator<uint32_t, NonZero, const uint32_t*>;
 using DdstIt = hipcub::TransformInputIterator<uint64_t, Widen, const uint32_t*>;
 
@@ -390,25 +385,25 @@ struct gpk_defragger6 {
   uint64_t cap = 0;
   Work w{};
   TimeWork tw{};
-  void* tmp = nullptr;
+  uint8_t* tmp = nullptr;
   size_t tmp_bytes = 0;
+  gpk::Workspace ws;
 };
 
 namespace {
 
-void free_all(gpk_defragger6* d) {
-  for (void* p : {(void*)d->w.info, (void*)d->w.listed, (void*)d->w.dsize, (void*)d->w.dpay, (void*)d->w.dhead,
-                  (void*)d->w.dnum, (void*)d->w.ddst, (void*)d->w.ppos, (void*)d->w.fin, (void*)d->w.fin_len,
-                  (void*)d->w.desc, (void*)d->tw.key_seen, (void*)d->tw.dead, d->tmp})
-    if (p) (void)hipFree(p);
+void carve(gpk_defragger6* d) {  // every device array of the handle
+  const uint64_t n = d->cap;
+  d->ws.take(d->w.info, n), d->ws.take(d->w.desc, 2 * n), d->ws.take(d->w.listed, n), d->ws.take(d->w.dsize, n);
+  d->ws.take(d->w.dpay, n), d->ws.take(d->w.dhead, n), d->ws.take(d->w.dnum, n), d->ws.take(d->w.ddst, n);
+  d->ws.take(d->w.ppos, n), d->ws.take(d->w.fin, n), d->ws.take(d->w.fin_len, n), d->ws.take(d->tw.key_seen, n);
+  d->ws.take(d->tw.dead, n), d->ws.take(d->tmp, d->tmp_bytes);
 }
 
 }  // namespace
 
 extern "C" int gpk_defragger6_create(gpk_defragger6** out, int device, uint64_t max_packets) {
-  if (!out || max_packets == 0 || max_packets >= (1ull << 28)) return GPK_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GPK_ENODEV;
+  if (const int rc = gpk::check_create(out, device, max_packets)) return rc;
   gpk::DeviceScope dscope(device);  // the caller's device is restored on return
   if (dscope.err != hipSuccess) return GPK_EHIP;
   gpk_defragger6* d = new (std::nothrow) gpk_defragger6();
@@ -423,21 +418,13 @@ extern "C" int gpk_defragger6_create(gpk_defragger6** out, int device, uint64_t 
                 hipSuccess &&
             hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)n) ==
                 hipSuccess;
-  d->tmp_bytes = std::max(std::max(b0, b1), std::max(b2, (size_t)16));
-  Work& w = d->w;
-  ok = ok && hipMalloc((void**)&w.info, n * 16) == hipSuccess && hipMalloc((void**)&w.desc, n * 32) == hipSuccess &&
-       hipMalloc((void**)&w.listed, n * 4) == hipSuccess && hipMalloc((void**)&w.dsize, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.dpay, n * 4) == hipSuccess && hipMalloc((void**)&w.dhead, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.dnum, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.ddst, n * 8) == hipSuccess && hipMalloc((void**)&w.ppos, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.fin, n * 4) == hipSuccess && hipMalloc((void**)&w.fin_len, n * 4) == hipSuccess &&
-       hipMalloc((void**)&d->tw.key_seen, n * 8) == hipSuccess && hipMalloc((void**)&d->tw.dead, n * 4) == hipSuccess &&
-       hipMalloc(&d->tmp, d->tmp_bytes) == hipSuccess;
-  if (!ok) {
-    free_all(d);
+  d->tmp_bytes = gpk::max_temp({b0, b1, b2});
+  carve(d);
+  if (!ok || !d->ws.alloc()) {
     delete d;
     return GPK_ENOMEM;
   }
+  carve(d);
   *out = d;
   return GPK_OK;
 }
@@ -446,7 +433,7 @@ extern "C" int gpk_defragger6_destroy(gpk_defragger6* d) {
   if (!d) return GPK_EINVAL;
   gpk::DeviceScope dscope(d->device);
   (void)hipDeviceSynchronize();
-  free_all(d);
+  d->ws.release();
   delete d;
   return GPK_OK;
 }

@@ -27,8 +27,9 @@
 #include <new>
 
 #include "../../include/gpk_flows.h"
-#include "gpk_devguard.h"
 #include "gpk_frag6.h"
+#include "gpk_scan.h"
+#include "gpk_workspace.h"
 
 // gpk_host.cpp: gpk_decode_batch with the fused key derivation (library-internal)
 extern "C" int gpk_decode_batch_keys(gpk_ctx* c, const gpk_parser* p, const gpk_batch* b, const gpk_results* o, int key_kind,
@@ -314,7 +315,7 @@ __global__ void __launch_bounds__(256) pack_bytes_kernel(const uint8_t* data, co
   }
 }
 
-struct Widen64 {
+struct Widen64 {  // gpk_scan.h's Widen under the name that pack's scan kernels carry
   __host__ __device__ uint64_t operator()(uint32_t v) const { return v; }
 };
 
@@ -361,11 +362,20 @@ struct gpk_grouper {
   uint32_t* iota = nullptr;
   uint32_t* heads = nullptr;
   uint32_t* gid = nullptr;
-  void* tmp = nullptr;
+  uint8_t* tmp = nullptr;
   size_t tmp_bytes = 0;
+  gpk::Workspace ws;
 };
 
 namespace {
+
+void carve(gpk_grouper* g) {  // every device array of the handle
+  const uint64_t n = g->cap;
+  g->ws.take(g->keys, n * kKeyWords), g->ws.take(g->hash, n), g->ws.take(g->code, n), g->ws.take(g->slot_of, n);
+  g->ws.take(g->table, g->tsize), g->ws.take(g->bucket_min, 1u << 16), g->ws.take(g->brank, 1u << 16);
+  g->ws.take(g->f, n), g->ws.take(g->fs, n), g->ws.take(g->iota, n), g->ws.take(g->heads, n), g->ws.take(g->gid, n);
+  g->ws.take(g->tmp, g->tmp_bytes);
+}
 
 int end_bit(uint64_t n) {  // bits to hold 0..n
   int b = 1;
@@ -373,21 +383,13 @@ int end_bit(uint64_t n) {  // bits to hold 0..n
   return b;
 }
 
-void free_all(gpk_grouper* g) {
-  for (void* p : {(void*)g->keys, (void*)g->hash, (void*)g->code, (void*)g->slot_of, (void*)g->table,
-                  (void*)g->bucket_min, (void*)g->brank, (void*)g->f, (void*)g->fs, (void*)g->iota,
-                  (void*)g->heads, (void*)g->gid, g->tmp})
-    if (p) (void)hipFree(p);
-}
-
 }  // namespace
 
 static int group_rest(gpk_grouper* g, uint64_t n, int kind, const gpk_groups& o, hipStream_t s);
 
 extern "C" int gpk_grouper_create(gpk_grouper** out, int device, uint64_t max_packets) {
-  if (!out || max_packets == 0 || max_packets >= (1ull << kIdxBits)) return GPK_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GPK_ENODEV;
+  static_assert(kIdxBits == 28, "check_create bounds max_packets by the table word's index field");
+  if (const int rc = gpk::check_create(out, device, max_packets)) return rc;
   gpk::DeviceScope dscope(device);  // the caller's device is restored on return
   if (dscope.err != hipSuccess) return GPK_EHIP;
   gpk_grouper* g = new (std::nothrow) gpk_grouper();
@@ -402,21 +404,13 @@ extern "C" int gpk_grouper_create(gpk_grouper** out, int device, uint64_t max_pa
                                                (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 32) == hipSuccess &&
             hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n) ==
                 hipSuccess;
-  g->tmp_bytes = std::max(sort_bytes, scan_bytes);
-  ok = ok && hipMalloc((void**)&g->keys, n * kKeyWords * 4) == hipSuccess &&
-       hipMalloc((void**)&g->hash, n * 8) == hipSuccess && hipMalloc((void**)&g->code, n * 4) == hipSuccess &&
-       hipMalloc((void**)&g->slot_of, n * 4) == hipSuccess &&
-       hipMalloc((void**)&g->table, g->tsize * 8) == hipSuccess &&
-       hipMalloc((void**)&g->bucket_min, (1u << 16) * 4) == hipSuccess &&
-       hipMalloc((void**)&g->brank, (1u << 16) * 4) == hipSuccess &&
-       hipMalloc((void**)&g->f, n * 4) == hipSuccess && hipMalloc((void**)&g->fs, n * 4) == hipSuccess &&
-       hipMalloc((void**)&g->iota, n * 4) == hipSuccess && hipMalloc((void**)&g->heads, n * 4) == hipSuccess &&
-       hipMalloc((void**)&g->gid, n * 4) == hipSuccess && hipMalloc(&g->tmp, g->tmp_bytes) == hipSuccess;
-  if (!ok) {
-    free_all(g);
+  g->tmp_bytes = gpk::max_temp({sort_bytes, scan_bytes});
+  carve(g);
+  if (!ok || !g->ws.alloc()) {
     delete g;
     return GPK_ENOMEM;
   }
+  carve(g);
   *out = g;
   return GPK_OK;
 }
@@ -425,7 +419,7 @@ extern "C" int gpk_grouper_destroy(gpk_grouper* g) {
   if (!g) return GPK_EINVAL;
   gpk::DeviceScope dscope(g->device);
   (void)hipDeviceSynchronize();
-  free_all(g);
+  g->ws.release();
   delete g;
   return GPK_OK;
 }

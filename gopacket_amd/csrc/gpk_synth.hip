@@ -16,6 +16,7 @@
 
 #include <cstring>
 
+#include "gpk_scan.h"
 #include "gpk_synth.h"
 
 using namespace gpk_synth;
@@ -50,10 +51,6 @@ struct DevSink {
     acc |= b << (8 * k);
     mask |= 1u << k;
   }
-};
-
-struct Widen {
-  __host__ __device__ uint64_t operator()(uint32_t x) const { return x; }
 };
 
 struct HostSink {

@@ -38,8 +38,8 @@
 //      pend_kernel    the pages still listed, by group
 //   6. emit_kernel    one wave per chunk: its record goes to its stream-major
 //                     place, its bytes move with destination-aligned 16-byte
-//                     stores, the source realigned in registers (copy_bytes, as
-//                     in gpk_defrag.hip).
+//                     stores, the source realigned in registers (copy_bytes of
+//                     gpk_copy.h).
 // Every state variable of a key is computed identically by all 64 lanes from
 // shuffled or broadcast values, so the control flow around ballots, shuffles
 // and barriers is wave-uniform; blocks of the plan kernel are one wave.
@@ -50,7 +50,9 @@
 #include <new>
 
 #include "../../include/gpk_tcpasm.h"
-#include "gpk_devguard.h"
+#include "gpk_copy.h"
+#include "gpk_scan.h"
+#include "gpk_workspace.h"
 
 namespace {
 
@@ -640,48 +642,6 @@ __global__ void __launch_bounds__(256) pend_kernel(const uint32_t* start, const 
   }
 }
 
-// dst[0..n) = src[0..n) by one wave (as in gpk_defrag.hip). Every 16-byte load
-// is aligned and holds at least one byte of the source, so it stays inside the
-// pages the source is in.
-template <int Q>
-__device__ __forceinline__ void copy_vectors(uint4* d, const uint4* sa, uint32_t nvec, uint32_t r, uint32_t lane) {
-  for (uint32_t v = lane; v < nvec; v += 64) {
-    const uint4 A = sa[v], B = sa[v + 1];
-    const uint32_t w[8] = {A.x, A.y, A.z, A.w, B.x, B.y, B.z, B.w};
-    uint4 out;
-    out.x = (uint32_t)((((uint64_t)w[Q + 1] << 32) | w[Q]) >> r);
-    out.y = (uint32_t)((((uint64_t)w[Q + 2] << 32) | w[Q + 1]) >> r);
-    out.z = (uint32_t)((((uint64_t)w[Q + 3] << 32) | w[Q + 2]) >> r);
-    out.w = (uint32_t)((((uint64_t)w[Q + 4] << 32) | w[Q + 3]) >> r);
-    d[v] = out;
-  }
-}
-
-__device__ __forceinline__ void copy_bytes(uint8_t* dst, const uint8_t* src, uint32_t n, uint32_t lane) {
-  uint32_t head = (uint32_t)(-(uintptr_t)dst & 15);
-  if (head > n) head = n;
-  const uint32_t body = n - head, nvec = body >> 4, tail = body & 15;
-  uint8_t* d16 = dst + head;
-  const uint8_t* s16 = src + head;
-  if (lane < head) dst[lane] = src[lane];
-  if (lane >= 16 && lane < 16 + tail) d16[nvec * 16 + lane - 16] = s16[nvec * 16 + lane - 16];
-  if (!nvec) return;
-  const uint32_t sh = (uint32_t)((uintptr_t)s16 & 15);
-  const uint4* sa = (const uint4*)(s16 - sh);
-  uint4* d = (uint4*)d16;
-  if (sh == 0) {
-    for (uint32_t v = lane; v < nvec; v += 64) d[v] = sa[v];
-    return;
-  }
-  const uint32_t r = (sh & 3) * 8;
-  switch (sh >> 2) {  // wave-uniform: one source phase per chunk
-    case 0: copy_vectors<0>(d, sa, nvec, r, lane); break;
-    case 1: copy_vectors<1>(d, sa, nvec, r, lane); break;
-    case 2: copy_vectors<2>(d, sa, nvec, r, lane); break;
-    default: copy_vectors<3>(d, sa, nvec, r, lane); break;
-  }
-}
-
 struct EmitArgs {
   const uint8_t* data;
   const uint64_t* offsets;
@@ -708,7 +668,7 @@ __global__ void __launch_bounds__(256) emit_kernel(EmitArgs a) {
       a.o.chunks[idx] = c;
     }
     if (!c.len || at + a.w.s_nbytes[cr] > a.o.data_cap) continue;  // a stream that does not fit is not written at all
-    copy_bytes(a.o.data + at + local, a.data + a.offsets[c.src] + a.w.info[c.src].z + c.src_off, c.len, lane);
+    gpk::copy_bytes(a.o.data + at + local, a.data + a.offsets[c.src] + a.w.info[c.src].z + c.src_off, c.len, lane);
   }
 }
 
@@ -718,48 +678,43 @@ struct gpk_tcpasm {
   int device = 0;
   uint64_t cap = 0;
   Work w{};
-  void* tmp = nullptr;
+  uint8_t* tmp = nullptr;
   size_t tmp_bytes = 0;
+  gpk::Workspace ws;      // the arrays by packet: fixed at create
+  gpk::Workspace slices;  // the arrays by workspace slot: replaced when a batch needs more slots
 };
 
 namespace {
 
-void free_slices(gpk_tcpasm* d) {
-  for (void* p : {(void*)d->w.wc, (void*)d->w.pg_seq, (void*)d->w.pg_pkt, (void*)d->w.pg_meta})
-    if (p) (void)hipFree(p);
-  d->w.wc = nullptr;
-  d->w.pg_seq = d->w.pg_pkt = d->w.pg_meta = nullptr;
-  d->w.wcap = 0;
-}
-
-bool alloc_slices(gpk_tcpasm* d, uint64_t wcap) {
+void carve(gpk_tcpasm* d) {
   Work& w = d->w;
-  const bool ok = hipMalloc((void**)&w.wc, wcap * sizeof(gpk_tcp_chunk)) == hipSuccess &&
-                  hipMalloc((void**)&w.pg_seq, wcap * 4) == hipSuccess &&
-                  hipMalloc((void**)&w.pg_pkt, wcap * 4) == hipSuccess &&
-                  hipMalloc((void**)&w.pg_meta, wcap * 4) == hipSuccess;
-  if (ok)
-    w.wcap = wcap;
-  else
-    free_slices(d);
-  return ok;
+  gpk::Workspace& ws = d->ws;
+  const uint64_t n = d->cap;
+  ws.take(w.info, n), ws.take(w.creator, n), ws.take(w.s_made, n), ws.take(w.s_nchunks, n), ws.take(w.s_nbytes, n);
+  ws.take(w.s_wk0, n), ws.take(w.s_closed, n), ws.take(w.s_group, n), ws.take(w.snum, n), ws.take(w.cbase, n);
+  ws.take(w.dbase, n), ws.take(w.g_creator, n), ws.take(w.g_npend, n), ws.take(w.g_head, n), ws.take(w.pbase, n);
+  ws.take(w.wbase, n + 1), ws.take(d->tmp, d->tmp_bytes);
 }
 
-void free_all(gpk_tcpasm* d) {
-  free_slices(d);
-  for (void* p : {(void*)d->w.info, (void*)d->w.creator, (void*)d->w.s_made, (void*)d->w.s_nchunks,
-                  (void*)d->w.s_nbytes, (void*)d->w.s_wk0, (void*)d->w.s_closed, (void*)d->w.s_group, (void*)d->w.snum,
-                  (void*)d->w.cbase, (void*)d->w.dbase, (void*)d->w.g_creator, (void*)d->w.g_npend, (void*)d->w.g_head,
-                  (void*)d->w.pbase, (void*)d->w.wbase, d->tmp})
-    if (p) (void)hipFree(p);
+void carve_slices(gpk_tcpasm* d, uint64_t wcap) {
+  Work& w = d->w;
+  d->slices.take(w.wc, wcap), d->slices.take(w.pg_seq, wcap), d->slices.take(w.pg_pkt, wcap);
+  d->slices.take(w.pg_meta, wcap);
+}
+
+bool alloc_slices(gpk_tcpasm* d, uint64_t wcap) {  // replaces them; on failure the handle has none (wcap 0)
+  d->slices.release();
+  carve_slices(d, wcap);
+  const bool ok = d->slices.alloc();
+  carve_slices(d, wcap);
+  d->w.wcap = ok ? wcap : 0;
+  return ok;
 }
 
 }  // namespace
 
 extern "C" int gpk_tcpasm_create(gpk_tcpasm** out, int device, uint64_t max_packets) {
-  if (!out || max_packets == 0 || max_packets >= (1ull << 28)) return GPK_EINVAL;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GPK_ENODEV;
+  if (const int rc = gpk::check_create(out, device, max_packets)) return rc;
   gpk::DeviceScope dscope(device);  // the caller's device is restored on return
   if (dscope.err != hipSuccess) return GPK_EHIP;
   gpk_tcpasm* d = new (std::nothrow) gpk_tcpasm();
@@ -775,22 +730,14 @@ extern "C" int gpk_tcpasm_create(gpk_tcpasm** out, int device, uint64_t max_pack
                 hipSuccess &&
             hipcub::DeviceScan::ExclusiveSum(nullptr, b2, (const uint64_t*)nullptr, (uint64_t*)nullptr, (int)n) ==
                 hipSuccess;
-  d->tmp_bytes = std::max(std::max(b0, b1), std::max(b2, (size_t)16));
-  Work& w = d->w;
-  ok = ok && hipMalloc((void**)&w.info, n * 16) == hipSuccess && hipMalloc((void**)&w.creator, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.s_made, n * 4) == hipSuccess && hipMalloc((void**)&w.s_nchunks, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.s_nbytes, n * 8) == hipSuccess && hipMalloc((void**)&w.s_wk0, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.s_closed, n * 4) == hipSuccess && hipMalloc((void**)&w.s_group, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.snum, n * 4) == hipSuccess && hipMalloc((void**)&w.cbase, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.dbase, n * 8) == hipSuccess && hipMalloc((void**)&w.g_creator, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.g_npend, n * 4) == hipSuccess && hipMalloc((void**)&w.g_head, n * 4) == hipSuccess &&
-       hipMalloc((void**)&w.pbase, n * 4) == hipSuccess && hipMalloc((void**)&w.wbase, (n + 1) * 4) == hipSuccess &&
-       hipMalloc(&d->tmp, d->tmp_bytes) == hipSuccess && alloc_slices(d, 2 * n);
-  if (!ok) {
-    free_all(d);
+  d->tmp_bytes = gpk::max_temp({b0, b1, b2});
+  carve(d);
+  if (!ok || !d->ws.alloc() || !alloc_slices(d, 2 * n)) {
+    d->ws.release();
     delete d;
     return GPK_ENOMEM;
   }
+  carve(d);
   *out = d;
   return GPK_OK;
 }
@@ -799,7 +746,8 @@ extern "C" int gpk_tcpasm_destroy(gpk_tcpasm* d) {
   if (!d) return GPK_EINVAL;
   gpk::DeviceScope dscope(d->device);
   (void)hipDeviceSynchronize();
-  free_all(d);
+  d->slices.release();
+  d->ws.release();
   delete d;
   return GPK_OK;
 }
@@ -832,7 +780,6 @@ int tcpasm_run(gpk_tcpasm* d, const gpk_batch* b, const gpk_results* r, const gp
   if (want_w >= (1ull << 32)) return GPK_EINVAL;
   if (want_w > d->w.wcap) {  // the workspace serves one call at a time: nothing of it is in flight
     if (hipDeviceSynchronize() != hipSuccess) return GPK_EHIP;
-    free_slices(d);
     if (!alloc_slices(d, want_w)) return GPK_ENOMEM;
   }
   const Work& w = d->w;

@@ -52,33 +52,62 @@ NONE, USELESS, FRAG_TOO_SMALL, FRAG_OFFSET, FRAG_OVERRUN, UNKNOWN = (
     _lib.GROUP_FRAG_OVERRUN, _lib.GROUP_UNKNOWN)
 
 
-class Grouper:
+class _Handle:
+    """Owns a handle of the C ABI: made by the entry `_create`(&h, device,
+    max_packets), released by the entry `_destroy`(h)."""
+    _create = _destroy = None
+
     def __init__(self, max_packets, device=0):
         self.h = ctypes.c_void_p()
-        _lib.check(_lib.lib().gpk_grouper_create(ctypes.byref(self.h), device, int(max_packets)))
+        _lib.check(getattr(_lib.lib(), self._create)(ctypes.byref(self.h), device, int(max_packets)))
         self.max_packets = int(max_packets)
+
+    def close(self):
+        if self.h:
+            getattr(_lib.lib(), self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _out_buffer(data, data_cap, out_data, dev):
+    """-> (out_data, cap): the caller's output bytes, or ones of data_cap (default: the batch's size) + 16 spare."""
+    import torch
+    if out_data is None:
+        cap = int(data.numel() if data_cap is None else data_cap)
+        return torch.empty(cap + 16, dtype=torch.uint8, device=dev), cap
+    return out_data, int(out_data.numel() if data_cap is None else data_cap)
+
+
+class Grouper(_Handle):
+    _create, _destroy = "gpk_grouper_create", "gpk_grouper_destroy"
+
+    @staticmethod
+    def _outputs(offsets):
+        import torch
+        n, dev = offsets.numel(), offsets.device
+        return dict(group_of=torch.empty(n, dtype=torch.int32, device=dev),
+                    perm=torch.empty(n, dtype=torch.int32, device=dev),
+                    start=torch.empty(n + 1, dtype=torch.int32, device=dev),
+                    first=torch.empty(max(n, 1), dtype=torch.int32, device=dev),
+                    counts=torch.zeros(2, dtype=torch.int32, device=dev))
 
     def group(self, data, offsets, caplens, records, layouts=None, flows=None, kind=CONNECTION, buckets=8,
               out=None, stream=None):
         """Device tensors in (torch, as gpk_decode_batch takes them); returns
         dict(group_of, perm, start, first, counts) of device tensors (or fills `out`)."""
-        import torch
-        n = offsets.numel()
-        dev = offsets.device
         if out is None:
-            out = dict(group_of=torch.empty(n, dtype=torch.int32, device=dev),
-                       perm=torch.empty(n, dtype=torch.int32, device=dev),
-                       start=torch.empty(n + 1, dtype=torch.int32, device=dev),
-                       first=torch.empty(max(n, 1), dtype=torch.int32, device=dev),
-                       counts=torch.zeros(2, dtype=torch.int32, device=dev))
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+            out = self._outputs(offsets)
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, flows.data_ptr() if flows is not None else None,
                          layouts.data_ptr() if layouts is not None else None)
-        g = _lib.Groups(out["group_of"].data_ptr(), out["perm"].data_ptr(), out["start"].data_ptr(),
-                        out["first"].data_ptr(), out["counts"].data_ptr())
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        g = _lib.Groups.of(out)
         _lib.check(_lib.lib().gpk_group_batch(self.h, ctypes.byref(b), ctypes.byref(r), int(kind), int(buckets),
-                                              ctypes.byref(g), sp))
+                                              ctypes.byref(g), _lib.stream_ptr(stream)))
         return out
 
     def decode_group(self, ctx, parser, data, offsets, caplens, records, err_args=None, flows=None, kind=CONNECTION,
@@ -86,23 +115,14 @@ class Grouper:
         """gpk_decode_group_batch: decode (records/err_args/flows as
         Context.decode_device, no layouts) and group by `kind` (CONNECTION or
         DEFRAG) with the key derived inside the decode kernel."""
-        import torch
-        n = offsets.numel()
-        dev = offsets.device
         if out is None:
-            out = dict(group_of=torch.empty(n, dtype=torch.int32, device=dev),
-                       perm=torch.empty(n, dtype=torch.int32, device=dev),
-                       start=torch.empty(n + 1, dtype=torch.int32, device=dev),
-                       first=torch.empty(max(n, 1), dtype=torch.int32, device=dev),
-                       counts=torch.zeros(2, dtype=torch.int32, device=dev))
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+            out = self._outputs(offsets)
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), err_args.data_ptr() if err_args is not None else None,
                          flows.data_ptr() if flows is not None else None, None)
-        g = _lib.Groups(out["group_of"].data_ptr(), out["perm"].data_ptr(), out["start"].data_ptr(),
-                        out["first"].data_ptr(), out["counts"].data_ptr())
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        g = _lib.Groups.of(out)
         _lib.check(_lib.lib().gpk_decode_group_batch(ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), self.h,
-                                                     int(kind), ctypes.byref(g), sp))
+                                                     int(kind), ctypes.byref(g), _lib.stream_ptr(stream)))
         return out
 
     def hashes(self, n):
@@ -123,17 +143,6 @@ class Grouper:
         start = out["start"][:G + 1].cpu().tolist()
         return [perm[start[g]:start[g + 1]] for g in range(G)], out["group_of"].cpu().tolist()
 
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_grouper_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def pack_batch(data, offsets, caplens, order, total_bytes=None, stream=None):
     """gpk_pack_batch: the packets `order` (device int32 tensor) of a device
@@ -146,8 +155,8 @@ def pack_batch(data, offsets, caplens, order, total_bytes=None, stream=None):
     out_d = torch.empty(total_bytes + 16, dtype=torch.uint8, device=dev)
     out_o = torch.empty(max(m, 1), dtype=torch.int64, device=dev)
     out_c = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
-    b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), offsets.numel(), data.numel())
-    sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+    b = _lib.Batch.of(data, offsets, caplens)
+    sp = _lib.stream_ptr(stream)
     _lib.check(_lib.lib().gpk_pack_batch(ctypes.byref(b), order.data_ptr() if m else None, m, out_d.data_ptr(),
                                          out_o.data_ptr(), out_c.data_ptr(), sp))
     return out_d, out_o[:m], out_c[:m]
@@ -181,7 +190,7 @@ HELD, EHOLE, EINVALID, EMAXLEN, EPANIC = (_lib.DEFRAG_HELD, _lib.DEFRAG_EHOLE, _
                                           _lib.DEFRAG_EMAXLEN, _lib.DEFRAG_EPANIC)
 
 
-class Defragmenter:
+class Defragmenter(_Handle):
     """gpk_defrag_batch (include/gpk_defrag.h): the datagrams
     ip4defrag.DefragIPv4 would have returned for a decoded, DEFRAG-grouped
     batch, every packet's verdict and the fragments still waiting. One call
@@ -189,10 +198,7 @@ class Defragmenter:
     `seen` (gpk_defrag_batch_timed) the keys keep LastSeen and
     DiscardOlderThan can run after the batch."""
 
-    def __init__(self, max_packets, device=0):
-        self.h = ctypes.c_void_p()
-        _lib.check(_lib.lib().gpk_defragger_create(ctypes.byref(self.h), device, int(max_packets)))
-        self.max_packets = int(max_packets)
+    _create, _destroy = "gpk_defragger_create", "gpk_defragger_destroy"
 
     def defrag(self, data, offsets, caplens, records, layouts, groups, data_cap=None, out_data=None, stream=None,
                seen=None, discard_older_than=None):
@@ -212,11 +218,7 @@ class Defragmenter:
         import torch
         n = offsets.numel()
         dev = offsets.device
-        if out_data is None:
-            cap = int(data.numel() if data_cap is None else data_cap)
-            out_data = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
-        else:
-            cap = int(out_data.numel() if data_cap is None else data_cap)
+        out_data, cap = _out_buffer(data, data_cap, out_data, dev)
         m = max(n, 1)
         out = dict(verdict=torch.empty(m, dtype=torch.int32, device=dev),
                    last=torch.empty(m, dtype=torch.int32, device=dev),
@@ -226,14 +228,13 @@ class Defragmenter:
                    payload_off=torch.empty(m, dtype=torch.int32, device=dev),
                    pending=torch.empty(m, dtype=torch.int32, device=dev),
                    counts=torch.zeros(4, dtype=torch.int64, device=dev), data=out_data)
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        g = _lib.Groups(groups["group_of"].data_ptr(), groups["perm"].data_ptr(), groups["start"].data_ptr(),
-                        groups["first"].data_ptr(), groups["counts"].data_ptr())
+        g = _lib.Groups.of(groups)
         d = _lib.Datagrams(out["verdict"].data_ptr(), out["last"].data_ptr(), out["length"].data_ptr(),
                            out["offsets"].data_ptr(), out["caplens"].data_ptr(), out["payload_off"].data_ptr(),
                            out["pending"].data_ptr(), out["counts"].data_ptr(), out_data.data_ptr(), cap)
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         if seen is None:
             if discard_older_than is not None:
                 raise ValueError("discard_older_than needs seen")
@@ -246,55 +247,71 @@ class Defragmenter:
         out["verdict"] = out["verdict"][:n]
         return out
 
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_defragger_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+def _prepend(carried, data, offsets, caplens, spare=0):
+    """The carried packets (data, offsets, caplens) put in front of a batch,
+    with `spare` zero bytes behind the data."""
+    import torch
+    pd, po, pc = carried
+    tail = [torch.zeros(spare, dtype=torch.uint8, device=offsets.device)] if spare else []
+    return torch.cat([pd, data] + tail), torch.cat([po, offsets + pd.numel()]), torch.cat([pc, caplens])
 
 
-class IPv4Defragmenter:
-    """A streaming ip4defrag.IPv4Defragmenter over device batches: the
-    fragments still waiting after a batch stay on the device and are put in
-    front of the next one (pack_batch of `pending`), which reproduces the
-    reference's state. Each call decodes (with layouts), groups and
-    reassembles pending + new packets; verdicts and `last` are mapped back to
-    the caller's indices (a datagram can only be completed by a new packet).
+def _decode_group(ctx, parser, grouper, data, offsets, caplens, kind):
+    """Decode a batch (with layouts) and group it by `kind` on the current
+    stream -> (records, layouts, groups, stream)."""
+    import torch
+    n, dev = offsets.numel(), offsets.device
+    rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
+    lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
+    flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
+    st = torch.cuda.current_stream()
+    ctx.decode_device(parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
+    return rec, lay, grouper.group(data, offsets, caplens, rec, lay, kind=kind, stream=st), st
 
-    timed=False keeps no time: flush() is then the caller's only
-    DiscardOlderThan. timed=True: defrag() takes the packets' timestamps
-    (int64 ns, greater than INT64_MIN), every key keeps its LastSeen on the
-    device beside its fragments, and discard_older_than(t) is
-    DiscardOlderThan(t)."""
+
+def _pack_carry(data, offsets, caplens, order, stream):
+    """pack_batch of the packets that go into the next call, cut to their bytes."""
+    import torch
+    total = int(caplens.index_select(0, order.long()).sum(dtype=torch.int64).item())
+    d2, o2, c2 = pack_batch(data, offsets, caplens, order, total_bytes=total, stream=stream)
+    return d2[:total], o2, c2
+
+
+class _StreamingDefragmenter:
+    """What IPv4Defragmenter and IPv6Defragmenter share: the fragments kept on
+    the device between calls, and a step that puts them in front of the batch,
+    decodes, groups, reassembles, packs what is still pending and maps the
+    results back to the caller's indices. A subclass gives the grouping kind,
+    the batch reassembler, the per-datagram keys, the reassembly call and, if
+    it has one, a filter on what stays pending."""
+    _kind = _reassembler = None
+    _per_datagram = ()  # the result's arrays with one entry per datagram; last and head are packet indices
 
     def __init__(self, ctx, parser, max_packets, device=0, timed=False):
         self.ctx, self.parser = ctx, parser
         self.max_packets = int(max_packets)
         self.timed = bool(timed)
         self.grouper = Grouper(self.max_packets, device)
-        self.defragmenter = Defragmenter(self.max_packets, device)
+        self.defragmenter = self._reassembler(self.max_packets, device)
         self._pending = None  # (data, offsets, caplens) on the device
-        self._pending_seen = None  # timed: int64[pending], the LastSeen of each carried fragment's key
+        self._pending_seen = None  # timed: int64[pending], the time (IPv4: LastSeen) of each carried fragment's key
 
     @property
     def pending_count(self):
         return 0 if self._pending is None else int(self._pending[1].numel())
 
     def flush(self):
-        """Forget every waiting fragment; returns how many there were."""
+        """Forget every waiting (held) fragment; returns how many there were."""
         k = self.pending_count
         self._pending = self._pending_seen = None
         return k
 
     def discard_older_than(self, t):
-        """DiscardOlderThan(t), t in int64 ns: the keys whose LastSeen < t are
-        forgotten with their fragments. Returns the number of keys discarded
-        (the reference's return value). timed=True only."""
+        """DiscardOlderThan(t), t in int64 ns: the keys whose LastSeen < t (IPv6:
+        whose last call was before t) are forgotten with their fragments. Returns
+        the number of keys discarded (the reference's return value). timed=True
+        only."""
         import torch
         if not self.timed:
             raise NotImplementedError("discard_older_than: time is out of scope unless timed=True")
@@ -309,23 +326,28 @@ class IPv4Defragmenter:
     def defrag(self, data, offsets, caplens, timestamps=None):
         """One batch of packets (device tensors: uint8 data, int64 offsets,
         int32 caplens; timed: int64 ns timestamps, one per packet). Returns
-        Defragmenter.defrag's dict for the caller's packets, with `verdict` and
-        `last` in the caller's indices and counts/pending on the host:
-        datagrams, data, offsets, caplens, ..."""
+        the batch reassembler's dict (Defragmenter.defrag's, Defragmenter6.defrag's)
+        for the caller's packets, with `verdict`, `last` (and IPv6's `head`) in
+        the caller's indices and counts/pending on the host: datagrams, data,
+        offsets, caplens, ..."""
         if self.timed != (timestamps is not None):
             raise ValueError("timestamps go with timed=True, and only with it")
         return self._step(data, offsets, caplens, timestamps, None)
+
+    def _reassemble(self, batch, groups, carried, stream, timed_args):
+        """-> (the reassembler's result, its counts on the host)"""
+        raise NotImplementedError
+
+    def _keep_pending(self, out, groups, pend, datagrams):
+        """A bool mask over `pend` of what stays pending, or None for all of it."""
+        return None
 
     def _step(self, data, offsets, caplens, timestamps, discard_t):
         import torch
         dev = offsets.device
         P = self.pending_count
         if P:
-            pd, po, pc = self._pending
-            base = pd.numel()
-            data = torch.cat([pd, data])
-            offsets = torch.cat([po, offsets + base])
-            caplens = torch.cat([pc, caplens])
+            data, offsets, caplens = _prepend(self._pending, data, offsets, caplens)
             if self.timed:
                 timestamps = torch.cat([self._pending_seen, timestamps])
         n = offsets.numel()
@@ -333,33 +355,27 @@ class IPv4Defragmenter:
             raise ValueError("pending + batch exceed max_packets")
         if n == 0:
             e32, e64 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
-            return dict(verdict=e32, last=e32, length=e32, offsets=e64, caplens=e32, payload_off=e32, pending=e32,
+            return dict(verdict=e32, **{k: e64 if k == "offsets" else e32 for k in self._per_datagram}, pending=e32,
                         counts=[0, 0, 0, 0], datagrams=0, data=torch.empty(0, dtype=torch.uint8, device=dev),
                         **(dict(pending_seen=e64, time_counts=[0, 0]) if self.timed else {}))
-        rec = torch.zeros(max(n, 1) * 16, dtype=torch.uint8, device=dev)
-        lay = torch.zeros(max(n, 1) * 64, dtype=torch.uint8, device=dev)
-        flw = torch.zeros(max(n, 1) * 3, dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream()
-        self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
-        groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=DEFRAG, stream=st)
-        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, stream=st,
-                                       seen=timestamps if self.timed else None, discard_older_than=discard_t)
-        counts = out["counts"].cpu().tolist()
+        rec, lay, groups, st = _decode_group(self.ctx, self.parser, self.grouper, data, offsets, caplens, self._kind)
+        tk = dict(seen=timestamps, discard_older_than=discard_t) if self.timed else {}
+        out, counts = self._reassemble((data, offsets, caplens, rec, lay), groups, P, st, tk)
         D, K = counts[0], counts[1]
         pend = out["pending"][:K]
-        if K:
-            total = int(caplens.index_select(0, pend.long()).sum(dtype=torch.int64).item())
-            d2, o2, c2 = pack_batch(data, offsets, caplens, pend, total_bytes=total, stream=st)
-            self._pending = (d2[:total], o2, c2)
-        else:
-            self._pending = None
+        pseen = out["pending_seen"][:K] if self.timed else None
+        keep = self._keep_pending(out, groups, pend, D) if K and D else None
+        if keep is not None:
+            pend = pend[keep]
+            if self.timed:
+                pseen = pseen[keep]
+            K = counts[1] = int(pend.numel())
+        self._pending = _pack_carry(data, offsets, caplens, pend.contiguous(), st) if K else None
         if self.timed:
-            self._pending_seen = out["pending_seen"][:K].clone() if K else None
-            out.update(pending_seen=out["pending_seen"][:K], time_counts=out["time_counts"].cpu().tolist())
-        v = out["verdict"][P:]
-        out.update(verdict=v, last=out["last"][:D] - P, length=out["length"][:D], offsets=out["offsets"][:D],
-                   caplens=out["caplens"][:D], payload_off=out["payload_off"][:D], pending=pend - P,
-                   counts=counts, datagrams=D)
+            self._pending_seen = pseen.clone() if K else None
+            out.update(pending_seen=pseen, time_counts=out["time_counts"].cpu().tolist())
+        per = {k: out[k][:D] - P if k in ("last", "head") else out[k][:D] for k in self._per_datagram}
+        out.update(verdict=out["verdict"][P:], **per, pending=pend - P, counts=counts, datagrams=D)
         return out
 
     def close(self):
@@ -367,10 +383,32 @@ class IPv4Defragmenter:
         self.defragmenter.close()
 
 
+class IPv4Defragmenter(_StreamingDefragmenter):
+    """A streaming ip4defrag.IPv4Defragmenter over device batches: the
+    fragments still waiting after a batch stay on the device and are put in
+    front of the next one (pack_batch of `pending`), which reproduces the
+    reference's state. Each call decodes (with layouts), groups and
+    reassembles pending + new packets; verdicts and `last` are mapped back to
+    the caller's indices (a datagram can only be completed by a new packet).
+
+    timed=False keeps no time: flush() is then the caller's only
+    DiscardOlderThan. timed=True: defrag() takes the packets' timestamps
+    (int64 ns, greater than INT64_MIN), every key keeps its LastSeen on the
+    device beside its fragments, and discard_older_than(t) is
+    DiscardOlderThan(t)."""
+
+    _kind, _reassembler = DEFRAG, Defragmenter
+    _per_datagram = ("last", "length", "offsets", "caplens", "payload_off")
+
+    def _reassemble(self, batch, groups, carried, stream, timed_args):
+        out = self.defragmenter.defrag(*batch, groups, stream=stream, **timed_args)
+        return out, out["counts"].cpu().tolist()
+
+
 HELD6, CARRIED6 = _lib.DEFRAG6_HELD, _lib.DEFRAG6_CARRIED
 
 
-class Defragmenter6:
+class Defragmenter6(_Handle):
     """gpk_defrag6_batch (include/gpk_defrag6.h): the IPv6 layers
     ip6defrag.DefragIPv6 would have returned for a decoded, DEFRAG6-grouped
     batch, every packet's verdict and the fragments it holds. One call behaves
@@ -379,10 +417,7 @@ class Defragmenter6:
     key). With `seen` (gpk_defrag6_batch_timed) the keys keep their time and
     DiscardOlderThan can run after the batch."""
 
-    def __init__(self, max_packets, device=0):
-        self.h = ctypes.c_void_p()
-        _lib.check(_lib.lib().gpk_defragger6_create(ctypes.byref(self.h), device, int(max_packets)))
-        self.max_packets = int(max_packets)
+    _create, _destroy = "gpk_defragger6_create", "gpk_defragger6_destroy"
 
     def defrag(self, data, offsets, caplens, records, layouts, groups, carry=0, data_cap=None, out_data=None,
                stream=None, seen=None, discard_older_than=None):
@@ -406,11 +441,7 @@ class Defragmenter6:
         import torch
         n = offsets.numel()
         dev = offsets.device
-        if out_data is None:
-            cap = int(data.numel() if data_cap is None else data_cap)
-            out_data = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
-        else:
-            cap = int(out_data.numel() if data_cap is None else data_cap)
+        out_data, cap = _out_buffer(data, data_cap, out_data, dev)
         m = max(n, 1)
         i32 = torch.int32
         out = dict(verdict=torch.empty(m, dtype=i32, device=dev), last=torch.empty(m, dtype=i32, device=dev),
@@ -419,14 +450,13 @@ class Defragmenter6:
                    caplens=torch.empty(m, dtype=i32, device=dev), payload_off=torch.empty(m, dtype=i32, device=dev),
                    pending=torch.empty(m, dtype=i32, device=dev),
                    counts=torch.zeros(4, dtype=torch.int64, device=dev), data=out_data)
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        g = _lib.Groups(groups["group_of"].data_ptr(), groups["perm"].data_ptr(), groups["start"].data_ptr(),
-                        groups["first"].data_ptr(), groups["counts"].data_ptr())
+        g = _lib.Groups.of(groups)
         d = _lib.Datagrams6(*[out[k].data_ptr() for k in ("verdict", "last", "head", "length", "offsets", "caplens",
                                                           "payload_off", "pending", "counts")],
                             out_data.data_ptr(), cap)
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         if seen is None:
             if discard_older_than is not None:
                 raise ValueError("discard_older_than needs seen")
@@ -439,19 +469,8 @@ class Defragmenter6:
         out["verdict"] = out["verdict"][:n]
         return out
 
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_defragger6_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class IPv6Defragmenter:
+class IPv6Defragmenter(_StreamingDefragmenter):
     """A streaming ip6defrag.IPv6Defragmenter over device batches: the listed
     fragments stay on the device (pack_batch of `pending`) and go in front of
     the next batch as its `carry` packets, which reproduces the reference's
@@ -473,115 +492,30 @@ class IPv6Defragmenter:
     returned a datagram in a call is not carried into the next one, so it does
     not return that datagram again in later batches and its state is freed."""
 
+    _kind, _reassembler = DEFRAG6, Defragmenter6
+    _per_datagram = ("last", "head", "length", "offsets", "caplens", "payload_off")
+
     def __init__(self, ctx, parser, max_packets, device=0, drop_completed=False, timed=False):
-        self.ctx, self.parser = ctx, parser
-        self.max_packets = int(max_packets)
+        super().__init__(ctx, parser, max_packets, device, timed)
         self.drop_completed = bool(drop_completed)
-        self.timed = bool(timed)
-        self.grouper = Grouper(self.max_packets, device)
-        self.defragmenter = Defragmenter6(self.max_packets, device)
-        self._pending = None  # (data, offsets, caplens) on the device
-        self._pending_seen = None  # timed: int64[pending], the time of each carried fragment's key
 
-    @property
-    def pending_count(self):
-        return 0 if self._pending is None else int(self._pending[1].numel())
-
-    def flush(self):
-        """Forget every held fragment; returns how many there were."""
-        k = self.pending_count
-        self._pending = self._pending_seen = None
-        return k
-
-    def discard_older_than(self, t):
-        """DiscardOlderThan(t), t in int64 ns: the keys whose last call was
-        before t are forgotten with their fragments. Returns the number of keys
-        discarded (the reference's return value). timed=True only."""
-        import torch
-        if not self.timed:
-            raise NotImplementedError("discard_older_than: time is out of scope unless timed=True")
-        if not self.pending_count:
-            return 0
-        dev = self._pending[1].device
-        out = self._step(torch.empty(0, dtype=torch.uint8, device=dev), torch.empty(0, dtype=torch.int64, device=dev),
-                         torch.empty(0, dtype=torch.int32, device=dev),
-                         torch.empty(0, dtype=torch.int64, device=dev), int(t))
-        return out["time_counts"][0]
-
-    def defrag(self, data, offsets, caplens, timestamps=None):
-        """One batch of packets (device tensors: uint8 data, int64 offsets,
-        int32 caplens; timed: int64 ns timestamps, one per packet). Returns
-        Defragmenter6.defrag's dict for the caller's packets, with `verdict`,
-        `last` and `head` in the caller's indices and counts/pending on the host:
-        datagrams, data, offsets, caplens, ..."""
-        if self.timed != (timestamps is not None):
-            raise ValueError("timestamps go with timed=True, and only with it")
-        return self._step(data, offsets, caplens, timestamps, None)
-
-    def _step(self, data, offsets, caplens, timestamps, discard_t):
-        import torch
-        dev = offsets.device
-        P = self.pending_count
-        if P:
-            pd, po, pc = self._pending
-            base = pd.numel()
-            data = torch.cat([pd, data])
-            offsets = torch.cat([po, offsets + base])
-            caplens = torch.cat([pc, caplens])
-            if self.timed:
-                timestamps = torch.cat([self._pending_seen, timestamps])
-        n = offsets.numel()
-        if n > self.max_packets:
-            raise ValueError("pending + batch exceed max_packets")
-        if n == 0:
-            e32, e64 = torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int64, device=dev)
-            return dict(verdict=e32, last=e32, head=e32, length=e32, offsets=e64, caplens=e32, payload_off=e32,
-                        pending=e32, counts=[0, 0, 0, 0], datagrams=0,
-                        data=torch.empty(0, dtype=torch.uint8, device=dev),
-                        **(dict(pending_seen=e64, time_counts=[0, 0]) if self.timed else {}))
-        rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
-        lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
-        flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream()
-        self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
-        groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=DEFRAG6, stream=st)
-        tk = dict(seen=timestamps, discard_older_than=discard_t) if self.timed else {}
-        out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, stream=st, **tk)
+    def _reassemble(self, batch, groups, carried, stream, timed_args):
+        out = self.defragmenter.defrag(*batch, groups, carry=carried, stream=stream, **timed_args)
         counts = out["counts"].cpu().tolist()
         if counts[3]:  # re-emission: the batch's size does not bound the datagrams' bytes
-            out = self.defragmenter.defrag(data, offsets, caplens, rec, lay, groups, carry=P, data_cap=counts[2],
-                                           stream=st, **tk)
+            out = self.defragmenter.defrag(*batch, groups, carry=carried, data_cap=counts[2], stream=stream,
+                                           **timed_args)
             counts = out["counts"].cpu().tolist()
-        D, K = counts[0], counts[1]
-        pend = out["pending"][:K]
-        pseen = out["pending_seen"][:K] if self.timed else None
-        if K and D and self.drop_completed:
-            gof = groups["group_of"].long()
-            done = torch.zeros(n, dtype=torch.bool, device=dev)
-            done[gof.index_select(0, out["last"][:D].long())] = True
-            keep = ~done.index_select(0, gof.index_select(0, pend.long()))
-            pend = pend[keep]
-            if self.timed:
-                pseen = pseen[keep]
-            K = int(pend.numel())
-        if K:
-            total = int(caplens.index_select(0, pend.long()).sum(dtype=torch.int64).item())
-            d2, o2, c2 = pack_batch(data, offsets, caplens, pend.contiguous(), total_bytes=total, stream=st)
-            self._pending = (d2[:total], o2, c2)
-        else:
-            self._pending = None
-        if self.timed:
-            self._pending_seen = pseen.clone() if K else None
-            out.update(pending_seen=pseen, time_counts=out["time_counts"].cpu().tolist())
-        counts[1] = K
-        out.update(verdict=out["verdict"][P:], last=out["last"][:D] - P, head=out["head"][:D] - P,
-                   length=out["length"][:D], offsets=out["offsets"][:D], caplens=out["caplens"][:D],
-                   payload_off=out["payload_off"][:D], pending=pend - P, counts=counts, datagrams=D)
-        return out
+        return out, counts
 
-    def close(self):
-        self.grouper.close()
-        self.defragmenter.close()
+    def _keep_pending(self, out, groups, pend, datagrams):
+        import torch
+        if not self.drop_completed:
+            return None
+        gof = groups["group_of"].long()
+        done = torch.zeros(gof.numel(), dtype=torch.bool, device=gof.device)
+        done[gof.index_select(0, out["last"][:datagrams].long())] = True
+        return ~done.index_select(0, gof.index_select(0, pend.long()))
 
 
 DIRECT, QUEUED, NOCONN, CARRIED, EBADCARRY, TCP_EPANIC = (
@@ -589,7 +523,7 @@ DIRECT, QUEUED, NOCONN, CARRIED, EBADCARRY, TCP_EPANIC = (
     _lib.TCPASM_EPANIC)
 
 
-class Assembler:
+class Assembler(_Handle):
     """gpk_tcpasm_batch (include/gpk_tcpasm.h): the Reassembly objects
     tcpassembly's Assembler would have handed every stream of a decoded,
     CONNECTION-grouped batch, the streams' bytes, every packet's verdict and
@@ -598,10 +532,7 @@ class Assembler:
     FlushAll() if `flush`. With `seen` (gpk_tcpasm_batch_timed) the connections
     keep lastSeen and FlushWithOptions{T} can run after the batch."""
 
-    def __init__(self, max_packets, device=0):
-        self.h = ctypes.c_void_p()
-        _lib.check(_lib.lib().gpk_tcpasm_create(ctypes.byref(self.h), device, int(max_packets)))
-        self.max_packets = int(max_packets)
+    _create, _destroy = "gpk_tcpasm_create", "gpk_tcpasm_destroy"
 
     def assemble(self, data, offsets, caplens, records, layouts, groups, max_pages=0, flush=False, data_cap=None,
                  stream=None, chunk_cap=None, out_data=None, carry_code=None, carry_seq=None, seen=None,
@@ -623,11 +554,7 @@ class Assembler:
         import torch
         n = offsets.numel()
         dev = offsets.device
-        if out_data is None:
-            cap = int(data.numel() if data_cap is None else data_cap)
-            out_data = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
-        else:
-            cap = int(out_data.numel() if data_cap is None else data_cap)
+        out_data, cap = _out_buffer(data, data_cap, out_data, dev)
         ccap = int(n + data.numel() // _lib.TCPASM_PAGE_BYTES if chunk_cap is None else chunk_cap)
         m, cm = max(n, 1), max(ccap, 1)
         i32, i64 = torch.int32, torch.int64
@@ -641,10 +568,9 @@ class Assembler:
                    conn_seq=torch.empty(m, dtype=i64, device=dev), conn_stream=torch.empty(m, dtype=i32, device=dev),
                    pend_pkt=torch.empty(cm, dtype=i32, device=dev), pend_page=torch.empty(cm, dtype=i32, device=dev),
                    counts=torch.zeros(8, dtype=i64, device=dev), data=out_data)
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        g = _lib.Groups(groups["group_of"].data_ptr(), groups["perm"].data_ptr(), groups["start"].data_ptr(),
-                        groups["first"].data_ptr(), groups["counts"].data_ptr())
+        g = _lib.Groups.of(groups)
         carried = 0 if carry_code is None else int(carry_code.numel())
         op = _lib.TcpasmOpts(int(max_pages), 1 if flush else 0, carried,
                              carry_code.data_ptr() if carried else None, carry_seq.data_ptr() if carried else None)
@@ -652,7 +578,7 @@ class Assembler:
             "verdict", "stream_of", "chunks", "stream_group", "stream_first", "stream_closed", "stream_chunk0",
             "stream_data0", "conn_seq", "conn_stream", "pend_pkt", "pend_page", "counts")], out_data.data_ptr(), ccap,
             cap)
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         if seen is None:
             if flush_older:
                 raise ValueError("flush_older needs seen")
@@ -670,17 +596,6 @@ class Assembler:
                                                          ctypes.byref(op), ctypes.byref(o), ctypes.byref(tm), sp))
         out["verdict"], out["stream_of"] = out["verdict"][:n], out["stream_of"][:n]
         return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_tcpasm_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class TCPAssembler:
@@ -760,12 +675,9 @@ class TCPAssembler:
         P = 0 if self._carry is None else len(self._carry[3])
         code = seq = None
         if P:
-            pd, po, pc, ccode, cseq, cgid, corigin = self._carry
-            base = pd.numel()
+            ccode, cseq, cgid, corigin = self._carry[3:]
             # 16 spare bytes: the byte mover's aligned loads may reach past the last payload
-            data = torch.cat([pd, data, torch.zeros(16, dtype=torch.uint8, device=dev)])
-            offsets = torch.cat([po, offsets + base])
-            caplens = torch.cat([pc, caplens])
+            data, offsets, caplens = _prepend(self._carry[:3], data, offsets, caplens, spare=16)
             code = torch.tensor(np.array(ccode, dtype=np.uint32).view(np.int32), dtype=torch.int32, device=dev)
             seq = torch.tensor(cseq, dtype=torch.int64, device=dev)
             if self.timed:
@@ -784,12 +696,7 @@ class TCPAssembler:
         if n == 0:
             return dict(verdict=[], stream_of=[], streams=[], data=torch.empty(0, dtype=torch.uint8, device=dev),
                         counts=[0] * 8, **(dict(flushed=0, closed=0) if self.timed else {}))
-        rec = torch.zeros(n * 16, dtype=torch.uint8, device=dev)
-        lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
-        flw = torch.zeros(n * 3, dtype=torch.int64, device=dev)
-        st = torch.cuda.current_stream()
-        self.ctx.decode_device(self.parser, data, offsets, caplens, rec, None, flw, lay, stream=st)
-        groups = self.grouper.group(data, offsets, caplens, rec, lay, kind=CONNECTION, stream=st)
+        rec, lay, groups, st = _decode_group(self.ctx, self.parser, self.grouper, data, offsets, caplens, CONNECTION)
         out = self.assembler.assemble(data, offsets, caplens, rec, lay, groups, max_pages=self.max_pages, flush=flush,
                                       stream=st, carry_code=code, carry_seq=seq,
                                       **(dict(seen=timestamps, flush_older=flush_older, t=t) if self.timed else {}))
@@ -876,9 +783,7 @@ class TCPAssembler:
                 norigin.append(origin(p))
         if order:
             ot = torch.tensor(order, dtype=torch.int32, device=dev)
-            total = int(caplens.index_select(0, ot.long()).sum(dtype=torch.int64).item())
-            d2, o2, c2 = pack_batch(data, offsets, caplens, ot, total_bytes=total, stream=st)
-            self._carry = (d2[:total], o2, c2, ncode, nseq, ngid, norigin)
+            self._carry = _pack_carry(data, offsets, caplens, ot, st) + (ncode, nseq, ngid, norigin)
             self._carry_seen = nseen if self.timed else None
         else:
             self._carry = self._carry_seen = None
@@ -889,17 +794,16 @@ class TCPAssembler:
         self.assembler.close()
 
 
-class Serializer:
+class Serializer(_Handle):
     """gpk_serialize_batch (include/gpk_serialize.h): gopacket.SerializeLayers for
     the packets of a decoded device batch, from their layouts and their (edited)
     gpk_fields records. Owns the handle and its scratch for up to max_packets
     output packets; device=None makes a host-only serializer (serialize_host)."""
 
+    _create, _destroy = "gpk_serializer_create", "gpk_serializer_destroy"
+
     def __init__(self, max_packets=1, device=0):
-        self.h = ctypes.c_void_p()
-        _lib.check(_lib.lib().gpk_serializer_create(ctypes.byref(self.h), -1 if device is None else int(device),
-                                                    int(max_packets)))
-        self.max_packets = int(max_packets)
+        super().__init__(max_packets, -1 if device is None else int(device))
 
     def serialize(self, data, offsets, caplens, layouts, fields, order=None, fix_lengths=False,
                   compute_checksums=False, out=None, out_cap=None, group=0, stream=None):
@@ -932,9 +836,9 @@ class Serializer:
                    status=torch.empty(m, dtype=torch.int32, device=dev),
                    err_args=torch.zeros(2 * m, dtype=torch.int32, device=dev),
                    counts=torch.zeros(4, dtype=torch.int64, device=dev))
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        b = _lib.Batch.of(data, offsets, caplens)
         o = _lib.SerializeOpts(int(bool(fix_lengths)), int(bool(compute_checksums)), int(group))
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         _lib.check(_lib.lib().gpk_serialize_batch(
             self.h, ctypes.byref(b), layouts.data_ptr(), fields.data_ptr(),
             order.data_ptr() if order is not None else None, m, ctypes.byref(o), out.data_ptr(), int(out_cap),
@@ -972,30 +876,20 @@ class Serializer:
             res["err_args"].ctypes.data, res["counts"].ctypes.data))
         return res
 
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_serializer_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Detunneler:
+class Detunneler(_Handle):
     """gpk_tunnel_batch (include/gpk_tunnel.h): one tunnel level peeled off a
     decoded device batch. Owns the workspace of the scans for up to max_packets
     packets; device=None makes a host-only one (peel_host)."""
 
+    _create, _destroy = "gpk_tunneler_create", "gpk_tunneler_destroy"
     KEYS = ("verdict", "class_start", "index", "in_offsets", "in_caplens", "tunnels", "counts")
 
     def __init__(self, max_packets=1, device=0):
-        self.h = ctypes.c_void_p()
-        if device is not None:
-            _lib.check(_lib.lib().gpk_tunneler_create(ctypes.byref(self.h), int(device), int(max_packets)))
-        self.max_packets = int(max_packets)
+        if device is None:  # host-only: no handle
+            self.h, self.max_packets = ctypes.c_void_p(), int(max_packets)
+        else:
+            super().__init__(max_packets, int(device))
 
     def set_sum_threshold(self, nbytes):
         """Lane group of the GRE sum: 64 lanes from `nbytes` on, 16 below."""
@@ -1021,10 +915,10 @@ class Detunneler:
                        in_caplens=torch.empty(n, dtype=torch.int32, device=dev),
                        tunnels=torch.empty(n * _lib.TUNNEL_DTYPE.itemsize, dtype=torch.uint8, device=dev),
                        counts=torch.zeros(8, dtype=torch.int32, device=dev))
-        b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
+        b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
         o = _lib.Tunnels(*[out[k].data_ptr() for k in self.KEYS])
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         _lib.check(_lib.lib().gpk_tunnel_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
                                                _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o), sp))
         return out
@@ -1054,14 +948,3 @@ class Detunneler:
         _lib.check(_lib.lib().gpk_tunnel_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
                                                     _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o)))
         return out
-
-    def close(self):
-        if self.h:
-            _lib.lib().gpk_tunneler_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

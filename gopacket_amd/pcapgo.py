@@ -808,7 +808,7 @@ class _WriterBase:
         b = _lib.Batch(data.data_ptr(), offsets.data_ptr(), caplens.data_ptr(), n, data.numel())
         o = self._now(now)
         o.group = int(group)
-        sp = None if stream is None else (stream if isinstance(stream, int) else stream.cuda_stream)
+        sp = _lib.stream_ptr(stream)
         for _ in range(2):
             out = torch.empty(cap + 16, dtype=torch.uint8, device=dev)
             _lib.check(self._L.gpk_capwrite_batch(

@@ -113,3 +113,14 @@ def test_host_view_is_a_view_and_does_not_grow_the_process():
         _lib.host_view(p, n, _lib.RECORD_DTYPE)
         _lib.host_view(p, 3 * n, np.uint64)
     assert _rss_mib() - r0 < 16
+
+
+def test_stream_ptr():
+    """None, a raw handle and a torch-like stream object."""
+    class Stream:
+        cuda_stream = 0x7F00DEAD0000
+
+    assert _lib.stream_ptr(None) is None
+    for raw in (0, 1, 0x7F00BEEF0000):
+        assert _lib.stream_ptr(raw) == raw and isinstance(_lib.stream_ptr(raw), int)
+    assert _lib.stream_ptr(Stream()) == Stream.cuda_stream
