@@ -116,6 +116,9 @@ EXPORTS = (
     # include/gpk_tunnel.h
     "gpk_tunneler_create", "gpk_tunneler_destroy", "gpk_tunnel_batch", "gpk_tunnel_batch_host",
     "gpk_tunneler_set_sum_threshold", "gpk_tunnel_format_error",
+    # include/gpk_control.h
+    "gpk_controller_create", "gpk_controller_destroy", "gpk_control_batch", "gpk_control_batch_host",
+    "gpk_controller_set_sum_threshold", "gpk_control_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -282,6 +285,32 @@ class Tunnels(ctypes.Structure):
     _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
                 ("in_offsets", ctypes.c_void_p), ("in_caplens", ctypes.c_void_p), ("tunnels", ctypes.c_void_p),
                 ("counts", ctypes.c_void_p)]
+
+
+# include/gpk_control.h constants
+LT_ARP, LT_ICMPV4, LT_ICMPV6, LT_ICMPV6_ECHO = 10, 19, 57, 132
+CTL_ICMP4, CTL_ICMP6, CTL_ICMP6ECHO, CTL_ARP, CTL_ALL = 1, 2, 4, 8, 15
+CTL_CSUM = 1
+CTL_NONE, CTL_UNKNOWN = -1, -2
+CTL_CLASS_ICMP4, CTL_CLASS_ICMP6, CTL_CLASS_ARP, CTL_CLASS_FAILED = range(4)
+CTL_NCLASS = 4
+(CTL_ERR_ICMP4_SHORT, CTL_ERR_ICMP6_SHORT, CTL_ERR_ECHO_SHORT, CTL_ERR_ARP_SHORT, CTL_ERR_ARP_EXPECTED) = range(80, 85)
+CTL_ST_TRUNCATED, CTL_ST_CSUM, CTL_ST_VALID, CTL_ST_NONET = 1, 2, 4, 8
+CTL_SUM_GROUP_BYTES = 8192
+# gpk_control (64 B): one candidate's control layers
+CONTROL_DTYPE = np.dtype([
+    ("kind", "u1"), ("err", "u1"), ("status", "u1"), ("nlayers", "u1"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("hdr_off", "<u4"), ("contents_len", "<u4"), ("payload_off", "<u4"), ("payload_len", "<u4"),
+    ("unsupported", "<i4"), ("layer_types", "<u2", (3,)), ("typecode", "<u2"), ("checksum", "<u2"),
+    ("correct", "<u2"), ("id", "<u2"), ("seq", "<u2"), ("arp_addr_type", "<u2"), ("arp_protocol", "<u2"),
+    ("arp_hw_size", "u1"), ("arp_prot_size", "u1"), ("arp_operation", "<u2"), ("next_type", "<i4"),
+    ("sum_init", "<u4")])
+
+
+class Controls(ctypes.Structure):
+    """gpk_controls: the outputs of gpk_control_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
 
 
 # include/gpk_afpacket.h constants
@@ -567,6 +596,12 @@ def lib():
         "gpk_tunnel_batch_host": ([vp, P(Batch), P(Results), u32, u32, P(Tunnels)], c_int),
         "gpk_tunneler_set_sum_threshold": ([vp, u32], c_int),
         "gpk_tunnel_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_controller_create": ([P(vp), c_int, u64], c_int),
+        "gpk_controller_destroy": ([vp], c_int),
+        "gpk_control_batch": ([vp, vp, vp, P(Batch), P(Results), u32, u32, P(Controls), vp], c_int),
+        "gpk_control_batch_host": ([vp, P(Batch), P(Results), u32, u32, P(Controls)], c_int),
+        "gpk_controller_set_sum_threshold": ([vp, u32], c_int),
+        "gpk_control_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

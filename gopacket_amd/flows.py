@@ -40,6 +40,9 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            VXLAN and Geneve headers of the packets whose decode
                                            stopped at one (layers/gre.go, vxlan.go, geneve.go),
                                            and their inner packets as zero-copy batches
+  ControlDecoder(max_packets).decode(...)  gpk_control_batch (include/gpk_control.h): the ICMPv4,
+                                           ICMPv6 (+Echo) and ARP layers of the packets whose
+                                           decode stopped in front of one, and their checksums
 """
 import ctypes
 
@@ -947,4 +950,74 @@ class Detunneler(_Handle):
         o = _lib.Tunnels(*[out[k].ctypes.data for k in Detunneler.KEYS])
         _lib.check(_lib.lib().gpk_tunnel_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
                                                     _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o)))
+        return out
+
+
+class ControlDecoder(_Handle):
+    """gpk_control_batch (include/gpk_control.h): the ICMPv4, ICMPv6,
+    ICMPv6Echo and ARP layers at the end of a decoded device batch. Owns the
+    workspace of the scans for up to max_packets packets; device=None makes a
+    host-only one (decode_host)."""
+
+    _create, _destroy = "gpk_controller_create", "gpk_controller_destroy"
+    KEYS = ("verdict", "class_start", "index", "records", "counts")
+
+    def __init__(self, max_packets=1, device=0):
+        if device is None:  # host-only: no handle
+            self.h, self.max_packets = ctypes.c_void_p(), int(max_packets)
+        else:
+            super().__init__(max_packets, int(device))
+
+    def set_sum_threshold(self, nbytes):
+        """Lane group of the sums: 64 lanes from `nbytes` on, 16 below."""
+        _lib.check(_lib.lib().gpk_controller_set_sum_threshold(self.h, int(nbytes)))
+
+    def decode(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True,
+               out=None, stream=None):
+        """Device tensors in: the batch (data 16-byte aligned and readable to
+        the next 16-byte boundary past its last packet), and the records and
+        layouts of ctx.decode_device(parser, ...) for it. Returns
+        dict(verdict[n], class_start[5], index[n], records[64 n] (uint8,
+        _lib.CONTROL_DTYPE), counts[8]) of device tensors (or fills `out`);
+        entries at and past counts[0] are not written."""
+        import torch
+        n = offsets.numel()
+        dev = offsets.device
+        if out is None:
+            out = dict(verdict=torch.empty(n, dtype=torch.int32, device=dev),
+                       class_start=torch.zeros(5, dtype=torch.int32, device=dev),
+                       index=torch.empty(n, dtype=torch.int32, device=dev),
+                       records=torch.empty(n * _lib.CONTROL_DTYPE.itemsize, dtype=torch.uint8, device=dev),
+                       counts=torch.zeros(8, dtype=torch.int32, device=dev))
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = _lib.Controls(*[out[k].data_ptr() for k in self.KEYS])
+        _lib.check(_lib.lib().gpk_control_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                                _lib.CTL_CSUM if checksum else 0, ctypes.byref(o),
+                                                _lib.stream_ptr(stream)))
+        return out
+
+    @staticmethod
+    def decode_host(data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_control_batch_host); `fill` is the byte the outputs start with."""
+        import numpy as np
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        caplens = np.ascontiguousarray(caplens, np.uint32)
+        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
+        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
+        n = len(caplens)
+
+        def arr(count, dt):
+            a = np.empty(count, dt)
+            a.view(np.uint8)[:] = fill
+            return a
+        out = dict(verdict=arr(n, np.int32), class_start=arr(5, np.uint32), index=arr(n, np.uint32),
+                   records=arr(n, _lib.CONTROL_DTYPE), counts=arr(8, np.uint32))
+        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
+        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
+        o = _lib.Controls(*[out[k].ctypes.data for k in ControlDecoder.KEYS])
+        _lib.check(_lib.lib().gpk_control_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                                     _lib.CTL_CSUM if checksum else 0, ctypes.byref(o)))
         return out

@@ -617,9 +617,12 @@ class DecodingLayerParser:
         """parser.go:238-241: replaces every registered decoder."""
         self._dlc = dlc
         inst = dlc._instances()
-        self._decoders = {k: d for k, d in inst.items() if not getattr(d, "tunnel_kind", 0)}  # kind -> instance
+        self._decoders = {k: d for k, d in inst.items()
+                          if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)}  # kind -> instance
         # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
         self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
+        # layers.ICMPv4 / ICMPv6 / ICMPv6Echo / ARP: decoded after the six-layer decode (gpk_control_batch), by GPK_CTL_* kind
+        self._controls = {d.control_kind: d for d in inst.values() if getattr(d, "control_kind", 0)}
         self._cfg = None
 
     def AddDecodingLayer(self, d):
@@ -659,12 +662,12 @@ class DecodingLayerParser:
         """Decode one packet on the GPU; fills the registered layers and the
         `decoded` list (truncated first, as parser.go:303-317 does)."""
         batch = PacketBatch.from_packets([data])
-        if self._tunnels:  # one packet: the host entry peels (gpk_tunnel_batch_host)
+        if self._tunnels or self._controls:  # one packet: the host entries (gpk_tunnel_batch_host, gpk_control_batch_host)
             return TunnelBatchResult(self, batch, _lib.OUT_ALL, True, device=False).Hydrate(0, decoded)
         res = self.DecodeBatch(batch, layouts=True)
         return res.Hydrate(0, decoded)
 
-    def DecodeBatch(self, batch, layouts=False, outputs=_lib.OUT_ALL, fields=False, gre_checksum=True):
+    def DecodeBatch(self, batch, layouts=False, outputs=_lib.OUT_ALL, fields=False, gre_checksum=True, checksum=True):
         """DecodeLayers for every packet of the batch on the device. fields=True
         also returns each packet's scalar layer fields and IPv4/TCP option maps
         computed on the device (BatchResult.fields, FIELDS_DTYPE;
@@ -675,11 +678,17 @@ class DecodingLayerParser:
         A parser that holds layers.GRE, VXLAN or Geneve returns a
         TunnelBatchResult instead: the outer decode, then up to
         MAX_TUNNEL_LEVELS times a peel (gpk_tunnel_batch) and the decode of
-        each inner class, all on the device (layouts are always kept)."""
-        if self._tunnels:
+        each inner class, all on the device (layouts are always kept).
+
+        A parser that holds layers.ICMPv4, ICMPv6, ICMPv6Echo or ARP returns
+        a TunnelBatchResult too: after each decode the control pass
+        (gpk_control_batch) appends those layers to the packets whose decode
+        stopped in front of one; checksum=True also makes their
+        VerifyChecksum on the device."""
+        if self._tunnels or self._controls:
             if fields:
-                raise ValueError("fields=True is not available for a parser with tunnel layers")
-            return TunnelBatchResult(self, batch, outputs, gre_checksum)
+                raise ValueError("fields=True is not available for a parser with tunnel or control layers")
+            return TunnelBatchResult(self, batch, outputs, gre_checksum, checksum=checksum)
         cfg = self._config(outputs)
         if fields:
             r, f = self.ctx().decode_host_fields(cfg, batch.data, batch.offsets, batch.caplens, layouts=layouts)
@@ -952,10 +961,13 @@ class TunnelPart:
     slices as a PacketBatch over the level-0 data (no byte is moved); result:
     the BatchResult of this slice batch (records, err_args, flows, layouts),
     i.e. the level's own checksum and flow outputs; peel: gpk_tunnel_batch's
-    outputs for it (host arrays), the tunnel headers found at its end."""
+    outputs for it (host arrays), the tunnel headers found at its end;
+    control: gpk_control_batch's outputs for it (host arrays), or None when
+    the parser holds no control layer."""
 
-    def __init__(self, first, index, batch, result, peel):
+    def __init__(self, first, index, batch, result, peel, control=None):
         self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
+        self.control = control
 
 
 class TunnelBatchResult:
@@ -965,28 +977,38 @@ class TunnelBatchResult:
     Level(k): the TunnelParts of level k, whose batches go to a Grouper,
     Assembler, BPF or WritePackets as any batch does."""
 
-    def __init__(self, parser, batch, outputs=_lib.OUT_ALL, gre_checksum=True, device=True):
+    def __init__(self, parser, batch, outputs=_lib.OUT_ALL, gre_checksum=True, device=True, checksum=True):
         self.parser, self.batch = parser, batch
         self.levels = []
         self._chain = [[] for _ in range(len(batch))]
         kinds = 0
         for k in parser._tunnels:
             kinds |= k
+        self._ctl_kinds, self._ctl_checksum = 0, checksum
+        for k in parser._controls:
+            self._ctl_kinds |= k
         run = self._run_device if device else self._run_host
         run(outputs, kinds, gre_checksum)
 
     def _clone(self, first):
         import copy
         p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
-        p.first, p._tunnels, p._cfg = LayerType(first), {}, None
+        p.first, p._tunnels, p._controls, p._cfg = LayerType(first), {}, {}, None
         return p
 
-    def _add_part(self, level, first, index, offsets, caplens, r, peel):
+    @staticmethod
+    def _no_peel(n):
+        """gpk_tunnel_batch's outputs for a parser without tunnel layers: no candidate."""
+        return dict(verdict=np.full(n, _lib.TUN_NONE, np.int32), class_start=np.zeros(7, np.uint32),
+                    counts=np.zeros(8, np.uint32), index=np.zeros(0, np.uint32), in_offsets=np.zeros(0, np.uint64),
+                    in_caplens=np.zeros(0, np.uint32), tunnels=np.zeros(0, _lib.TUNNEL_DTYPE))
+
+    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None):
         if len(self.levels) <= level:
             self.levels.append([])
         p = self._clone(first)
         part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
-                          BatchResult(p, None, r), peel)
+                          BatchResult(p, None, r), peel, control)
         part.result.batch = part.batch
         self.levels[level].append(part)
         for pos, g in enumerate(index):
@@ -1012,7 +1034,7 @@ class TunnelBatchResult:
         return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
 
     def _run_host(self, outputs, kinds, gre_checksum):
-        from .flows import Detunneler
+        from .flows import ControlDecoder, Detunneler
         b = self.batch
         work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
         level = 0
@@ -1023,22 +1045,26 @@ class TunnelBatchResult:
                 cfg = p._config(outputs)
                 dec = self.parser._host_decoder  # tests without a GPU put the decode oracle here
                 r = dec(p, b.data, offs, caps) if dec else p.ctx().decode_host(cfg, b.data, offs, caps, layouts=True)
-                pl = Detunneler.peel_host(b.data, offs, caps, r["records"], r["layouts"], cfg, kinds, gre_checksum)
-                part = self._add_part(level, first, index, offs, caps, r, pl)
+                pl = Detunneler.peel_host(b.data, offs, caps, r["records"], r["layouts"], cfg, kinds, gre_checksum) \
+                    if kinds else self._no_peel(len(index))
+                ctl = ControlDecoder.decode_host(b.data, offs, caps, r["records"], r["layouts"], cfg, self._ctl_kinds,
+                                                 self._ctl_checksum) if self._ctl_kinds else None
+                part = self._add_part(level, first, index, offs, caps, r, pl, ctl)
                 for lt, js in self._next_work(part, level):
                     nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
             work, level = nxt, level + 1
 
     def _run_device(self, outputs, kinds, gre_checksum):
         import torch
-        from .flows import Detunneler
+        from .flows import ControlDecoder, Detunneler
         b = self.batch
         ctx = self.parser.ctx()
         dev = torch.device("cuda", ctx.device)
         host = np.zeros((len(b.data) + 15) // 16 * 16 + 16, np.uint8)
         host[:len(b.data)] = b.data
         data = torch.from_numpy(host).to(dev)
-        det = Detunneler(max(len(b), 1), ctx.device)
+        det = Detunneler(max(len(b), 1), ctx.device) if kinds else None
+        ctd = ControlDecoder(max(len(b), 1), ctx.device) if self._ctl_kinds else None
         try:
             work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
                      torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
@@ -1054,11 +1080,26 @@ class TunnelBatchResult:
                     fl = torch.zeros(3 * n, dtype=torch.int64, device=dev)
                     lay = torch.zeros(n * 64, dtype=torch.uint8, device=dev)
                     ctx.decode_device(cfg, data, offs, caps, rec, err, fl, lay)
-                    out = det.peel(ctx, data, offs, caps, rec, lay, cfg, kinds, gre_checksum)
+                    out = det.peel(ctx, data, offs, caps, rec, lay, cfg, kinds, gre_checksum) if det else None
+                    cout = ctd.decode(ctx, data, offs, caps, rec, lay, cfg, self._ctl_kinds, self._ctl_checksum) \
+                        if ctd else None
                     torch.cuda.synchronize(dev)
                     r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
                              err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
                              layouts=lay.cpu().numpy().view(_lib.LAYOUT_DTYPE))
+                    ctl = None
+                    if cout is not None:
+                        cm = int(cout["counts"][0].item())
+                        ctl = dict(verdict=cout["verdict"].cpu().numpy(),
+                                   class_start=cout["class_start"].cpu().numpy().view(np.uint32),
+                                   counts=cout["counts"].cpu().numpy().view(np.uint32),
+                                   index=cout["index"][:cm].cpu().numpy().view(np.uint32),
+                                   records=cout["records"][:cm * _lib.CONTROL_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.CONTROL_DTYPE))
+                    if out is None:
+                        self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
+                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl)
+                        continue
                     m = int(out["counts"][0].item())
                     pl = dict(verdict=out["verdict"].cpu().numpy(),
                               class_start=out["class_start"].cpu().numpy().view(np.uint32),
@@ -1069,7 +1110,7 @@ class TunnelBatchResult:
                               tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
                                   _lib.TUNNEL_DTYPE))
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                          caps.cpu().numpy().view(np.uint32), r, pl)
+                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl)
                     for lt, js in self._next_work(part, level):
                         if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
                             io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
@@ -1079,7 +1120,9 @@ class TunnelBatchResult:
                         nxt.append((lt, index[pl["index"][js]], io, ic))
                 work, level = nxt, level + 1
         finally:
-            det.close()
+            for h in (det, ctd):
+                if h is not None:
+                    h.close()
 
     def __len__(self):
         return len(self.batch)
@@ -1092,6 +1135,17 @@ class TunnelBatchResult:
         v = int(part.peel["verdict"][pos])
         return part.peel["tunnels"][v] if v >= 0 else None
 
+    def _control(self, part, pos):
+        """The gpk_control record of a part's packet, or None: not a candidate."""
+        if part.control is None:
+            return None
+        v = int(part.control["verdict"][pos])
+        return part.control["records"][v] if v >= 0 else None
+
+    def Control(self, i):
+        """The gpk_control record (CONTROL_DTYPE) of packet i, or None."""
+        return self._control(*self._chain[i][-1])
+
     def Decoded(self, i):
         out = []
         for part, pos in self._chain[i]:
@@ -1099,13 +1153,18 @@ class TunnelBatchResult:
             t = self._tunnel(part, pos)
             if t is not None and not int(t["err"]):
                 out.append(LayerType(_TUN_LAYER_TYPE[int(t["kind"])]))
+            c = self._control(part, pos)
+            if c is not None:
+                out += [LayerType(int(x)) for x in c["layer_types"][:int(c["nlayers"])]]
         return out
 
     def Truncated(self, i):
         tr = False
         for part, pos in self._chain[i]:
             t = self._tunnel(part, pos)
-            tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED))
+            c = self._control(part, pos)
+            tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED)) \
+                or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED))
         return tr
 
     def Err(self, i):
@@ -1113,6 +1172,15 @@ class TunnelBatchResult:
         layers in the parser: the innermost level's."""
         part, pos = self._chain[i][-1]
         t = self._tunnel(part, pos)
+        c = self._control(part, pos)
+        if c is not None:  # the control layers' loop ended the decode: its error, the type it returned, or nil
+            if int(c["err"]):
+                buf = ctypes.create_string_buffer(256)
+                _lib.lib().gpk_control_format_error(int(c["err"]), int(c["err_a0"]), int(c["err_a1"]), buf, 256)
+                return GoError(buf.value.decode())
+            if int(c["unsupported"]) and not self.parser.IgnoreUnsupported:
+                return UnsupportedLayerType(int(c["unsupported"]))
+            return None
         if t is None:
             return part.result.Err(pos)
         code = int(t["err"])
@@ -1143,6 +1211,15 @@ class TunnelBatchResult:
             t = self._tunnel(part, pos)
             if t is not None and not int(t["err"]):
                 p._tunnels[int(t["kind"])]._from_record(t, part.batch.packet(pos))
+            c = self._control(part, pos)
+            if c is not None and int(c["nlayers"]):
+                pkt = part.batch.packet(pos)
+                p._controls[int(c["kind"])]._from_record(c, pkt)
+                if int(c["nlayers"]) > 1 and int(c["layer_types"][1]) == _lib.LT_ICMPV6_ECHO:
+                    p._controls[_lib.CTL_ICMP6ECHO]._from_record(c, pkt)
+                elif int(c["nlayers"]) > 1:  # gopacket.Payload
+                    o = int(c["payload_off"])
+                    p._decoders[_lib.DEC_PAYLOAD]._hydrate(pkt[o:o + int(c["payload_len"])])
         decoded[:] = self.Decoded(i)
         p.Truncated = self.Truncated(i)
         return self.Err(i)

@@ -2,7 +2,10 @@
 the DecodingLayer structs Ethernet, Dot1Q, IPv4, IPv6, IPv6ExtensionSkipper,
 TCP, UDP (layers/{ethernet,dot1q,ip4,ip6,tcp,udp}.go), and the three tunnel
 layers GRE, VXLAN, Geneve (layers/{gre,vxlan,geneve}.go), which are filled from
-the gpk_tunnel record of gpk_tunnel_batch (include/gpk_tunnel.h).
+the gpk_tunnel record of gpk_tunnel_batch (include/gpk_tunnel.h), and the four
+control layers ICMPv4, ICMPv6, ICMPv6Echo, ARP (layers/{icmp4,icmp6,icmp6msg,
+arp}.go), filled from the gpk_control record of gpk_control_batch
+(include/gpk_control.h).
 
 These structs are filled from device results, in one of two ways:
 - _fill(pkt, s, e, f): from the gpk_fields record the device wrote for the
@@ -61,6 +64,18 @@ LayerTypeENIP = _lt("ENIP")
 LayerTypeGRE = _lt("GRE")
 LayerTypeVXLAN = _lt("VXLAN")
 LayerTypeGeneve = _lt("Geneve")
+LayerTypeICMPv6 = _lt("ICMPv6")
+LayerTypeICMPv6RouterSolicitation = _lt("ICMPv6RouterSolicitation")
+LayerTypeICMPv6RouterAdvertisement = _lt("ICMPv6RouterAdvertisement")
+LayerTypeICMPv6NeighborSolicitation = _lt("ICMPv6NeighborSolicitation")
+LayerTypeICMPv6NeighborAdvertisement = _lt("ICMPv6NeighborAdvertisement")
+LayerTypeICMPv6Redirect = _lt("ICMPv6Redirect")
+LayerTypeICMPv6Echo = _lt("ICMPv6Echo")
+LayerTypeMLDv1MulticastListenerReport = _lt("MLDv1MulticastListenerReport")
+LayerTypeMLDv1MulticastListenerDone = _lt("MLDv1MulticastListenerDone")
+LayerTypeMLDv1MulticastListenerQuery = _lt("MLDv1MulticastListenerQuery")
+LayerTypeMLDv2MulticastListenerReport = _lt("MLDv2MulticastListenerReport")
+LayerTypeMLDv2MulticastListenerQuery = _lt("MLDv2MulticastListenerQuery")
 # layertypes.go:200-206
 LayerClassIPv6Extension = LayerClass([LayerTypeIPv6HopByHop, LayerTypeIPv6Routing, LayerTypeIPv6Fragment,
                                       LayerTypeIPv6Destination])
@@ -1356,3 +1371,177 @@ class Geneve(_TunnelLayer):
             ln = (b3 & 0x1f) * 4 + 4
             self.Options.append(GeneveOption(_be16(pkt, h + o), pkt[h + o + 2], b3 >> 5, ln, pkt[h + o + 4:h + o + ln]))
             o = (o + ln) & 0xff
+
+
+# ---- control layers: layers/icmp4.go, icmp6.go, icmp6msg.go, arp.go ---------------
+# A DecodingLayerParser that holds one of these decodes them on the device
+# after the six-layer decode (gpk_control_batch); the structs are filled from
+# the packet's gpk_control record and its bytes (_from_record).
+class _ControlLayer(BaseLayer):
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("control layers decode through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+
+class _TypeCode(int):
+    """icmp4.go:51-62 / icmp6.go:62-73: the type in the high byte, the code in the low one."""
+
+    def Type(self):
+        return int(self) >> 8
+
+    def Code(self):
+        return int(self) & 0xFF
+
+
+class ICMPv4TypeCode(_TypeCode):
+    pass
+
+
+class ICMPv6TypeCode(_TypeCode):
+    pass
+
+
+def CreateICMPv4TypeCode(typ, code):
+    return ICMPv4TypeCode((typ & 0xFF) << 8 | (code & 0xFF))
+
+
+def CreateICMPv6TypeCode(typ, code):
+    return ICMPv6TypeCode((typ & 0xFF) << 8 | (code & 0xFF))
+
+
+def _control_checksum(t, checksum):
+    """The (err, ChecksumVerificationResult) of a gpk_control record, or None when no sum was asked for."""
+    from .gopacket import GoError
+    st = int(t["status"])
+    if st & _lib.CTL_ST_CSUM:
+        return (None, ChecksumVerificationResult(bool(st & _lib.CTL_ST_VALID), int(t["correct"]), checksum))
+    if st & _lib.CTL_ST_NONET:  # tcpip.go:55-57
+        return (GoError("TCP/IP layer 4 checksum cannot be computed without network layer... call "
+                        "SetNetworkLayerForChecksum to set which layer to use"), ChecksumVerificationResult())
+    return None
+
+
+class ICMPv4(_ControlLayer):
+    """icmp4.go:209-276"""
+    kind = 200 + _lib.CTL_ICMP4
+    control_kind = _lib.CTL_ICMP4
+
+    def __init__(self):
+        self.TypeCode = ICMPv4TypeCode(0)
+        self.Checksum = self.Id = self.Seq = 0
+        self._csum = None
+
+    def LayerType(self):
+        return LayerTypeICMPv4
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeICMPv4])
+
+    def NextLayerType(self):
+        return LayerTypePayload
+
+    def _from_record(self, t, pkt):
+        self.TypeCode = ICMPv4TypeCode(int(t["typecode"]))
+        self.Checksum, self.Id, self.Seq = int(t["checksum"]), int(t["id"]), int(t["seq"])
+        h, c = int(t["hdr_off"]), int(t["contents_len"])
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["payload_len"])]
+        self._csum = _control_checksum(t, self.Checksum)
+
+    def VerifyChecksum(self):
+        """icmp4.go:265-276: the device's sum when the batch was decoded with checksum=True, else computed here."""
+        if self._csum is not None:
+            return self._csum
+        from .gopacket import ComputeChecksum, FoldChecksum
+        correct = FoldChecksum((ComputeChecksum(self.Contents + self.Payload, 0) - self.Checksum) & 0xFFFFFFFF)
+        return None, ChecksumVerificationResult(correct == self.Checksum, correct, self.Checksum)
+
+
+class ICMPv6(_ControlLayer):
+    """icmp6.go:170-277"""
+    kind = 200 + _lib.CTL_ICMP6
+    control_kind = _lib.CTL_ICMP6
+
+    def __init__(self):
+        self.TypeCode = ICMPv6TypeCode(0)
+        self.Checksum = 0
+        self._next = LayerTypePayload
+        self._csum = None
+
+    def LayerType(self):
+        return LayerTypeICMPv6
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeICMPv6])
+
+    def NextLayerType(self):
+        """icmp6.go:230-261 (worked out on the device: gpk_control.next_type)"""
+        return self._next
+
+    def _from_record(self, t, pkt):
+        self.TypeCode = ICMPv6TypeCode(int(t["typecode"]))
+        self.Checksum = int(t["checksum"])
+        h, c = int(t["hdr_off"]), int(t["contents_len"])
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["payload_len"])]
+        self._next = LayerType(int(t["next_type"]))
+        self._csum = _control_checksum(t, self.Checksum)
+
+    def VerifyChecksum(self):
+        """icmp6.go:263-277 with the pseudo-header of the last network layer of
+        the decoded list (the device's sum). A batch decoded with
+        checksum=False has none: the reference's error for a layer without
+        SetNetworkLayerForChecksum."""
+        if self._csum is not None:
+            return self._csum
+        from .gopacket import GoError
+        return (GoError("TCP/IP layer 4 checksum cannot be computed without network layer... call "
+                        "SetNetworkLayerForChecksum to set which layer to use"), ChecksumVerificationResult())
+
+
+class ICMPv6Echo(_ControlLayer):
+    """icmp6msg.go:122-164. DecodeFromBytes sets no BaseLayer: Contents and Payload stay empty."""
+    kind = 200 + _lib.CTL_ICMP6ECHO
+    control_kind = _lib.CTL_ICMP6ECHO
+
+    def __init__(self):
+        self.Identifier = self.SeqNumber = 0
+
+    def LayerType(self):
+        return LayerTypeICMPv6Echo
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeICMPv6Echo])
+
+    def NextLayerType(self):
+        return LayerTypePayload
+
+    def _from_record(self, t, pkt):
+        self.Identifier, self.SeqNumber = int(t["id"]), int(t["seq"])
+        self.Contents = self.Payload = b""
+
+
+class ARP(_ControlLayer):
+    """arp.go:25-108"""
+    kind = 200 + _lib.CTL_ARP
+    control_kind = _lib.CTL_ARP
+
+    def __init__(self):
+        self.AddrType = self.Protocol = self.HwAddressSize = self.ProtAddressSize = self.Operation = 0
+        self.SourceHwAddress = self.SourceProtAddress = self.DstHwAddress = self.DstProtAddress = b""
+
+    def LayerType(self):
+        return LayerTypeARP
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeARP])
+
+    def NextLayerType(self):
+        return LayerTypePayload
+
+    def _from_record(self, t, pkt):
+        self.AddrType, self.Protocol = int(t["arp_addr_type"]), int(t["arp_protocol"])
+        self.HwAddressSize, self.ProtAddressSize = int(t["arp_hw_size"]), int(t["arp_prot_size"])
+        self.Operation = int(t["arp_operation"])
+        h, c, hw, pr = int(t["hdr_off"]), int(t["contents_len"]), self.HwAddressSize, self.ProtAddressSize
+        a = h + 8
+        self.SourceHwAddress, self.SourceProtAddress = pkt[a:a + hw], pkt[a + hw:a + hw + pr]
+        self.DstHwAddress, self.DstProtAddress = pkt[a + hw + pr:a + 2 * hw + pr], pkt[a + 2 * hw + pr:h + c]
+        self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["payload_len"])]
