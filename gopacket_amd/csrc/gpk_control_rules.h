@@ -2,8 +2,8 @@
 // kernels and gpk_control_batch_host (one __host__ __device__ source, so the CPU
 // suite checks the code the device runs).
 //
-//   candidate      tun::last_payload of gpk_tunnel_rules.h over the parser's
-//                  tables: the payload and next type of the last decoded layer
+//   candidate      tun::candidate of gpk_tunnel_rules.h over the parser's tables:
+//                  the payload and next type of the last decoded layer
 //   decode_icmp4 / decode_icmp6 / decode_echo / decode_arp
 //                  DecodeFromBytes of layers/{icmp4,icmp6,icmp6msg,arp}.go. Every
 //                  slice expression is guarded by the length check in front of
@@ -180,17 +180,11 @@ GPK_HD uint32_t start_value(uint32_t address_words, uint32_t length) {
 // GPK_CTL_UNKNOWN; c is written for a class.
 GPK_HD int control(const DevTables* T, uint32_t kinds, uint32_t flags, const uint8_t* p, uint32_t caplen,
                    const gpk_record& rec, const gpk_layout& L, Ctl& c) {
-  const uint32_t nl = (rec.status >> GPK_ST_NLAYERS_SHIFT) & GPK_ST_NLAYERS_MASK;
-  if (nl > GPK_MAX_INLINE_LAYERS) return GPK_CTL_UNKNOWN;
-  const uint32_t err = rec.status & GPK_ST_ERR_MASK;
-  if (nl == 0 || (err != GPK_ERR_NONE && err != GPK_ERR_UNSUPPORTED)) return GPK_CTL_NONE;
-  const int kind = tun::kind_of_code((uint32_t)(rec.layers >> (4 * (nl - 1))) & 15u);
-  if (kind == GPK_DEC_NONE || kind >= GPK_DEC_PAYLOAD) return GPK_CTL_NONE;
-  const uint32_t s = L.start[kind - 1], e = L.end[kind - 1];
-  if (s == GPK_LAYOUT_ABSENT || e > caplen || s > e) return GPK_CTL_NONE;
-  const tun::Pay pay = tun::last_payload(T, kind, p, s, e);
+  static_assert(GPK_CTL_NONE == GPK_TUN_NONE && GPK_CTL_UNKNOWN == GPK_TUN_UNKNOWN, "tun::candidate's verdicts");
+  tun::Pay pay;
+  if (const int no = tun::candidate(T, p, caplen, rec, L, pay)) return no;
   const uint32_t k = kind_of_type(pay.next) & kinds;
-  if (!k || pay.len == 0 || pay.off > caplen || pay.len > caplen - pay.off) return GPK_CTL_NONE;
+  if (!k) return GPK_CTL_NONE;
   c = ctl_init(k, pay.off);
   const uint8_t* d = p + pay.off;
   int cls;

@@ -7,6 +7,9 @@
 //                  without error (it is in the list), so only the success paths
 //                  of layers/{ethernet,dot1q,ip4,ip6,tcp,udp}.go are restated;
 //                  they mirror dec_* of gpk_device.h line by line.
+//   candidate      whether a decoded list ends in a layer with a payload inside
+//                  the packet, and last_payload of it (gpk_control_rules.h
+//                  starts from it too)
 //   decode_vxlan / decode_gre / decode_geneve
 //                  DecodeFromBytes of layers/{vxlan,gre,geneve}.go with Go's
 //                  bounds rules: data[i] needs i < len, data[:hi] needs hi <=
@@ -124,6 +127,25 @@ GPK_HD Pay last_payload(const DevTables* T, int kind, const uint8_t* p, uint32_t
       break;
   }
   return Pay{ro, rl, rn};
+}
+
+// What a pass over a decoded batch looks at: the payload and next type of the
+// list's last layer. 0: pay is set and lies inside caplen, not empty;
+// GPK_TUN_UNKNOWN: the list is longer than the record names; GPK_TUN_NONE: a
+// decode error, no layer with a payload, or a dirty layout slot.
+GPK_HD int candidate(const DevTables* T, const uint8_t* p, uint32_t caplen, const gpk_record& rec, const gpk_layout& L,
+                     Pay& pay) {
+  const uint32_t nl = (rec.status >> GPK_ST_NLAYERS_SHIFT) & GPK_ST_NLAYERS_MASK;
+  if (nl > GPK_MAX_INLINE_LAYERS) return GPK_TUN_UNKNOWN;
+  const uint32_t err = rec.status & GPK_ST_ERR_MASK;
+  if (nl == 0 || (err != GPK_ERR_NONE && err != GPK_ERR_UNSUPPORTED)) return GPK_TUN_NONE;
+  const int kind = kind_of_code((uint32_t)(rec.layers >> (4 * (nl - 1))) & 15u);
+  if (kind == GPK_DEC_NONE || kind >= GPK_DEC_PAYLOAD) return GPK_TUN_NONE;
+  const uint32_t s = L.start[kind - 1], e = L.end[kind - 1];
+  if (s == GPK_LAYOUT_ABSENT || e > caplen || s > e) return GPK_TUN_NONE;
+  pay = last_payload(T, kind, p, s, e);
+  if (pay.len == 0 || pay.off > caplen || pay.len > caplen - pay.off) return GPK_TUN_NONE;
+  return 0;
 }
 
 GPK_HD uint32_t kind_of_type(int32_t lt) {
@@ -282,17 +304,10 @@ GPK_HD void decode_geneve(const DevTables* T, const uint8_t* d, uint32_t len, ui
 // GPK_TUN_UNKNOWN; t is written for a class.
 GPK_HD int peel(const DevTables* T, uint32_t kinds, const uint8_t* p, uint32_t caplen, const gpk_record& rec,
                 const gpk_layout& L, Tun& t) {
-  const uint32_t nl = (rec.status >> GPK_ST_NLAYERS_SHIFT) & GPK_ST_NLAYERS_MASK;
-  if (nl > GPK_MAX_INLINE_LAYERS) return GPK_TUN_UNKNOWN;
-  const uint32_t err = rec.status & GPK_ST_ERR_MASK;
-  if (nl == 0 || (err != GPK_ERR_NONE && err != GPK_ERR_UNSUPPORTED)) return GPK_TUN_NONE;
-  const int kind = kind_of_code((uint32_t)(rec.layers >> (4 * (nl - 1))) & 15u);
-  if (kind == GPK_DEC_NONE || kind >= GPK_DEC_PAYLOAD) return GPK_TUN_NONE;
-  const uint32_t s = L.start[kind - 1], e = L.end[kind - 1];
-  if (s == GPK_LAYOUT_ABSENT || e > caplen || s > e) return GPK_TUN_NONE;
-  const Pay pay = last_payload(T, kind, p, s, e);
+  Pay pay;
+  if (const int no = candidate(T, p, caplen, rec, L, pay)) return no;
   const uint32_t tk = kind_of_type(pay.next) & kinds;
-  if (!tk || pay.len == 0 || pay.off > caplen || pay.len > caplen - pay.off) return GPK_TUN_NONE;
+  if (!tk) return GPK_TUN_NONE;
   t = tun_init(tk, pay.off);
   const uint8_t* d = p + pay.off;
   if (tk == GPK_TUN_VXLAN) decode_vxlan(d, pay.len, t);

@@ -41,9 +41,10 @@ struct Workspace {
   }
 };
 
-// What every gpk_*_create checks first; the caller then opens its DeviceScope (else GPK_EHIP).
-inline int check_create(const void* out, int device, uint64_t max_packets) {
-  if (!out || max_packets == 0 || max_packets >= (1ull << 28)) return GPK_EINVAL;
+// What every gpk_*_create checks first (max_packets < limit, as the handle's header documents);
+// the caller then opens its DeviceScope (else GPK_EHIP).
+inline int check_create(const void* out, int device, uint64_t max_packets, uint64_t limit = 1ull << 28) {
+  if (!out || max_packets == 0 || max_packets >= limit) return GPK_EINVAL;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return GPK_ENODEV;
   return GPK_OK;

@@ -880,13 +880,14 @@ class Serializer(_Handle):
         return res
 
 
-class Detunneler(_Handle):
-    """gpk_tunnel_batch (include/gpk_tunnel.h): one tunnel level peeled off a
-    decoded device batch. Owns the workspace of the scans for up to max_packets
-    packets; device=None makes a host-only one (peel_host)."""
+class _PostPass(_Handle):
+    """A pass over a decoded device batch that writes a compact list ordered by
+    class (csrc/gpk_postpass.h). A subclass names its entry points, its _lib
+    output struct, the flag that asks for the sums and OUTPUTS: (key, count for
+    n packets, numpy dtype) of every array of that struct, in its order."""
 
-    _create, _destroy = "gpk_tunneler_create", "gpk_tunneler_destroy"
-    KEYS = ("verdict", "class_start", "index", "in_offsets", "in_caplens", "tunnels", "counts")
+    _batch = _batch_host = _set_threshold = _Out = _FLAG = None
+    OUTPUTS = ()
 
     def __init__(self, max_packets=1, device=0):
         if device is None:  # host-only: no handle
@@ -895,8 +896,59 @@ class Detunneler(_Handle):
             super().__init__(max_packets, int(device))
 
     def set_sum_threshold(self, nbytes):
-        """Lane group of the GRE sum: 64 lanes from `nbytes` on, 16 below."""
-        _lib.check(_lib.lib().gpk_tunneler_set_sum_threshold(self.h, int(nbytes)))
+        """Lane group of the sums: 64 lanes from `nbytes` on, 16 below."""
+        _lib.check(getattr(_lib.lib(), self._set_threshold)(self.h, int(nbytes)))
+
+    def _device(self, ctx, data, offsets, caplens, records, layouts, parser, kinds, sums, out, stream):
+        import numpy as np
+        import torch
+        n, dev = offsets.numel(), offsets.device
+        if out is None:  # records as bytes, the rest as int32 / int64; the call zeroes class_start and counts
+            out = {}
+            for key, count, dt in self.OUTPUTS:
+                dt = np.dtype(dt)
+                out[key] = (torch.empty(count(n) * dt.itemsize, dtype=torch.uint8, device=dev) if dt.fields else
+                            torch.empty(count(n), dtype=torch.int64 if dt.itemsize == 8 else torch.int32, device=dev))
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = self._Out(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS])
+        entry = getattr(_lib.lib(), self._batch)
+        _lib.check(entry(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                         self._FLAG if sums else 0, ctypes.byref(o), _lib.stream_ptr(stream)))
+        return out
+
+    @classmethod
+    def _host(cls, data, offsets, caplens, records, layouts, parser, kinds, sums, fill):
+        import numpy as np
+        data = np.ascontiguousarray(data, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        caplens = np.ascontiguousarray(caplens, np.uint32)
+        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
+        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
+        n = len(caplens)
+        out = {key: np.empty(count(n), dt) for key, count, dt in cls.OUTPUTS}
+        for a in out.values():
+            a.view(np.uint8)[:] = fill
+        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
+        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
+        o = cls._Out(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS])
+        _lib.check(getattr(_lib.lib(), cls._batch_host)(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                                        cls._FLAG if sums else 0, ctypes.byref(o)))
+        return out
+
+
+class Detunneler(_PostPass):
+    """gpk_tunnel_batch (include/gpk_tunnel.h): one tunnel level peeled off a
+    decoded device batch. Owns the workspace of the scans for up to max_packets
+    packets; device=None makes a host-only one (peel_host)."""
+
+    _create, _destroy = "gpk_tunneler_create", "gpk_tunneler_destroy"
+    _batch, _batch_host, _set_threshold = "gpk_tunnel_batch", "gpk_tunnel_batch_host", "gpk_tunneler_set_sum_threshold"
+    _Out, _FLAG = _lib.Tunnels, _lib.TUN_GRE_CSUM
+    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 7, "u4"), ("index", lambda n: n, "u4"),
+               ("in_offsets", lambda n: n, "u8"), ("in_caplens", lambda n: n, "u4"),
+               ("tunnels", lambda n: n, _lib.TUNNEL_DTYPE), ("counts", lambda n: 8, "u4"))
+    KEYS = tuple(k for k, _, _ in OUTPUTS)
 
     def peel(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True,
              out=None, stream=None):
@@ -907,70 +959,28 @@ class Detunneler(_Handle):
         `out`); entries at and past counts[0] are not written. Class c's inner
         batch is (data, in_offsets[class_start[c]:class_start[c+1]],
         in_caplens[...]) for a parser whose first layer is the class's type."""
-        import torch
-        n = offsets.numel()
-        dev = offsets.device
-        if out is None:
-            out = dict(verdict=torch.empty(n, dtype=torch.int32, device=dev),
-                       class_start=torch.zeros(7, dtype=torch.int32, device=dev),
-                       index=torch.empty(n, dtype=torch.int32, device=dev),
-                       in_offsets=torch.empty(n, dtype=torch.int64, device=dev),
-                       in_caplens=torch.empty(n, dtype=torch.int32, device=dev),
-                       tunnels=torch.empty(n * _lib.TUNNEL_DTYPE.itemsize, dtype=torch.uint8, device=dev),
-                       counts=torch.zeros(8, dtype=torch.int32, device=dev))
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Tunnels(*[out[k].data_ptr() for k in self.KEYS])
-        sp = _lib.stream_ptr(stream)
-        _lib.check(_lib.lib().gpk_tunnel_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                               _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o), sp))
-        return out
+        return self._device(ctx, data, offsets, caplens, records, layouts, parser, kinds, gre_checksum, out, stream)
 
-    @staticmethod
-    def peel_host(data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True, fill=0):
+    @classmethod
+    def peel_host(cls, data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_tunnel_batch_host); `fill` is the byte the outputs start with."""
-        import numpy as np
-        data = np.ascontiguousarray(data, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        caplens = np.ascontiguousarray(caplens, np.uint32)
-        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
-        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
-        n = len(caplens)
-
-        def arr(count, dt):
-            a = np.empty(count, dt)
-            a.view(np.uint8)[:] = fill
-            return a
-        out = dict(verdict=arr(n, np.int32), class_start=arr(7, np.uint32), index=arr(n, np.uint32),
-                   in_offsets=arr(n, np.uint64), in_caplens=arr(n, np.uint32), tunnels=arr(n, _lib.TUNNEL_DTYPE),
-                   counts=arr(8, np.uint32))
-        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
-        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
-        o = _lib.Tunnels(*[out[k].ctypes.data for k in Detunneler.KEYS])
-        _lib.check(_lib.lib().gpk_tunnel_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                                    _lib.TUN_GRE_CSUM if gre_checksum else 0, ctypes.byref(o)))
-        return out
+        return cls._host(data, offsets, caplens, records, layouts, parser, kinds, gre_checksum, fill)
 
 
-class ControlDecoder(_Handle):
+class ControlDecoder(_PostPass):
     """gpk_control_batch (include/gpk_control.h): the ICMPv4, ICMPv6,
     ICMPv6Echo and ARP layers at the end of a decoded device batch. Owns the
     workspace of the scans for up to max_packets packets; device=None makes a
     host-only one (decode_host)."""
 
     _create, _destroy = "gpk_controller_create", "gpk_controller_destroy"
-    KEYS = ("verdict", "class_start", "index", "records", "counts")
-
-    def __init__(self, max_packets=1, device=0):
-        if device is None:  # host-only: no handle
-            self.h, self.max_packets = ctypes.c_void_p(), int(max_packets)
-        else:
-            super().__init__(max_packets, int(device))
-
-    def set_sum_threshold(self, nbytes):
-        """Lane group of the sums: 64 lanes from `nbytes` on, 16 below."""
-        _lib.check(_lib.lib().gpk_controller_set_sum_threshold(self.h, int(nbytes)))
+    _batch, _batch_host = "gpk_control_batch", "gpk_control_batch_host"
+    _set_threshold = "gpk_controller_set_sum_threshold"
+    _Out, _FLAG = _lib.Controls, _lib.CTL_CSUM
+    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 5, "u4"), ("index", lambda n: n, "u4"),
+               ("records", lambda n: n, _lib.CONTROL_DTYPE), ("counts", lambda n: 8, "u4"))
+    KEYS = tuple(k for k, _, _ in OUTPUTS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True,
                out=None, stream=None):
@@ -980,44 +990,10 @@ class ControlDecoder(_Handle):
         dict(verdict[n], class_start[5], index[n], records[64 n] (uint8,
         _lib.CONTROL_DTYPE), counts[8]) of device tensors (or fills `out`);
         entries at and past counts[0] are not written."""
-        import torch
-        n = offsets.numel()
-        dev = offsets.device
-        if out is None:
-            out = dict(verdict=torch.empty(n, dtype=torch.int32, device=dev),
-                       class_start=torch.zeros(5, dtype=torch.int32, device=dev),
-                       index=torch.empty(n, dtype=torch.int32, device=dev),
-                       records=torch.empty(n * _lib.CONTROL_DTYPE.itemsize, dtype=torch.uint8, device=dev),
-                       counts=torch.zeros(8, dtype=torch.int32, device=dev))
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Controls(*[out[k].data_ptr() for k in self.KEYS])
-        _lib.check(_lib.lib().gpk_control_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                                _lib.CTL_CSUM if checksum else 0, ctypes.byref(o),
-                                                _lib.stream_ptr(stream)))
-        return out
+        return self._device(ctx, data, offsets, caplens, records, layouts, parser, kinds, checksum, out, stream)
 
-    @staticmethod
-    def decode_host(data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True, fill=0):
+    @classmethod
+    def decode_host(cls, data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_control_batch_host); `fill` is the byte the outputs start with."""
-        import numpy as np
-        data = np.ascontiguousarray(data, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        caplens = np.ascontiguousarray(caplens, np.uint32)
-        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
-        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
-        n = len(caplens)
-
-        def arr(count, dt):
-            a = np.empty(count, dt)
-            a.view(np.uint8)[:] = fill
-            return a
-        out = dict(verdict=arr(n, np.int32), class_start=arr(5, np.uint32), index=arr(n, np.uint32),
-                   records=arr(n, _lib.CONTROL_DTYPE), counts=arr(8, np.uint32))
-        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
-        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
-        o = _lib.Controls(*[out[k].ctypes.data for k in ControlDecoder.KEYS])
-        _lib.check(_lib.lib().gpk_control_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                                     _lib.CTL_CSUM if checksum else 0, ctypes.byref(o)))
-        return out
+        return cls._host(data, offsets, caplens, records, layouts, parser, kinds, checksum, fill)

@@ -21,12 +21,17 @@ session for the comparison: boxes differ by several percent.
 import argparse
 import json
 import os
+import re
 import statistics
 import struct
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+# this pass's instantiation of a kernel template of csrc/gpk_postpass.h, by its demangled name
+OWN = r"\b%s_kernel<.*ControlPass>"
 
 
 def spread(xs):
@@ -46,10 +51,10 @@ def kernel_times(prof):
 
 
 def per_run(kern, runs, *needles):
-    """Device time per run of the kernels whose name holds one of `needles`."""
+    """Device time per run of the kernels whose name matches one of `needles` (regular expressions)."""
     tot, found = [0.0] * runs, False
     for name, v in kern.items():
-        if any(q in name for q in needles):
+        if any(re.search(q, name) for q in needles):
             if len(v) % runs:
                 return None
             k, found = len(v) // runs, True
@@ -154,17 +159,17 @@ def main():
                 sums()
                 torch.cuda.synchronize()
         kern = kernel_times(prof)
-        s16 = [x for k, v in kern.items() if "ctl_sum16_kernel" in k for x in v]
-        s64 = [x for k, v in kern.items() if "ctl_sum64_kernel" in k for x in v]
+        s16 = [x for k, v in kern.items() if re.search(OWN % "sum16", k) for x in v]
+        s64 = [x for k, v in kern.items() if re.search(OWN % "sum64", k) for x in v]
         both = [x + y for x, y in zip(s16, s64)] if len(s16) == len(s64) else []
         row = dict(batch=name, source=synth.NAMES[cfg], control_one_in=every, packets=n, candidates=counts[0],
                    class_counts=counts[1:5], sums_made=counts[5], batch_bytes=int(c.sum(dtype=torch.int64).item()),
                    summed_bytes=summed, pass_ms=spread(t["pass_ms"]),
                    pass_Mpps=spread([n / (x * 1e3) for x in t["pass_ms"]]),
                    pass_with_sums_ms=spread(t["pass_with_sums_ms"]),
-                   kernels_ms=dict(classify=per_run(kern, a.runs, "ctl_classify_kernel"),
-                                   scatter=per_run(kern, a.runs, "ctl_scatter_kernel"),
-                                   scan=per_run(kern, a.runs, "scan", "Scan", "ctl_finish_kernel"),
+                   kernels_ms=dict(classify=per_run(kern, a.runs, OWN % "classify"),
+                                   scatter=per_run(kern, a.runs, OWN % "scatter"),
+                                   scan=per_run(kern, a.runs, "scan", "Scan", r"\bfinish_kernel<%d>" % _lib.CTL_NCLASS),
                                    sum16=spread(s16), sum64=spread(s64), sum=spread(both)),
                    sum_GBps=spread([summed / (x * 1e6) for x in both]))
         res["rows"].append(row)

@@ -28,12 +28,17 @@ import argparse
 import ctypes
 import json
 import os
+import re
 import statistics
 import struct
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+
+
+# this pass's instantiation of a kernel template of csrc/gpk_postpass.h, by its demangled name
+OWN = r"\b%s_kernel<.*TunnelPass>"
 
 
 def spread(xs):
@@ -53,10 +58,10 @@ def kernel_times(prof):
 
 
 def per_run(kern, runs, *needles):
-    """Device time per run of the kernels whose name holds one of `needles`."""
+    """Device time per run of the kernels whose name matches one of `needles` (regular expressions)."""
     tot, found = [0.0] * runs, False
     for name, v in kern.items():
-        if any(q in name for q in needles):
+        if any(re.search(q, name) for q in needles):
             if len(v) % runs:
                 return None
             k, found = len(v) // runs, True
@@ -173,9 +178,10 @@ def main():
             row = dict(batch=synth.NAMES[cfg], tunnelled_one_in=every, packets=n, inner_packets=m,
                        batch_bytes=int(c.sum(dtype=torch.int64).item()), inner_bytes=inner_bytes,
                        peel_ms=spread(t["peel"]), peel_Mpps=spread([n / (x * 1e3) for x in t["peel"]]),
-                       peel_kernels_ms=dict(classify=per_run(kern, a.runs, "classify_kernel"),
-                                            scatter=per_run(kern, a.runs, "scatter_kernel"),
-                                            scan=per_run(kern, a.runs, "scan", "finish_kernel")),
+                       peel_kernels_ms=dict(classify=per_run(kern, a.runs, OWN % "classify"),
+                                            scatter=per_run(kern, a.runs, OWN % "scatter"),
+                                            scan=per_run(kern, a.runs, "scan",
+                                                         r"\bfinish_kernel<%d>" % _lib.TUN_NCLASS)),
                        inner_decode_ms=dict(zero_copy=spread(t["zero_copy"]), pack=spread(t["pack"]),
                                             packed=spread(t["packed"]),
                                             pack_plus_packed=spread([x + y for x, y in zip(t["pack"], t["packed"])])),
@@ -231,8 +237,8 @@ def main():
                     fr()
                 torch.cuda.synchronize()
         kern = kernel_times(prof)
-        s16 = [x for k, v in kern.items() if "gre_sum16_kernel" in k for x in v]
-        s64 = [x for k, v in kern.items() if "gre_sum64_kernel" in k for x in v]
+        s16 = [x for k, v in kern.items() if re.search(OWN % "sum16", k) for x in v]
+        s64 = [x for k, v in kern.items() if re.search(OWN % "sum64", k) for x in v]
         f = [x for k, v in kern.items() if "frame_kernel" in k for x in v]
         return sums, summed, payload, s16, s64, f
 
