@@ -119,6 +119,8 @@ EXPORTS = (
     # include/gpk_control.h
     "gpk_controller_create", "gpk_controller_destroy", "gpk_control_batch", "gpk_control_batch_host",
     "gpk_controller_set_sum_threshold", "gpk_control_format_error",
+    # include/gpk_dns.h
+    "gpk_dns_decoder_create", "gpk_dns_decoder_destroy", "gpk_dns_batch", "gpk_dns_batch_host", "gpk_dns_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -311,6 +313,35 @@ class Controls(ctypes.Structure):
     """gpk_controls: the outputs of gpk_control_batch."""
     _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
                 ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p)]
+
+
+# include/gpk_dns.h constants
+LT_DNS = 107
+DNS_KIND, DNS_ALL = 1, 1
+DNS_NONE, DNS_UNKNOWN = -1, -2
+DNS_CLASS_OK, DNS_CLASS_FAILED = range(2)
+DNS_NCLASS = 2
+DNS_ERR_FIRST, DNS_ERR_END = 90, 121  # gpk_dns_err: GPK_DNS_ERR_SHORT .. GPK_DNS_ERR_DNSKEY_SMALL
+DNS_ST_TRUNCATED, DNS_ST_DROPPED = 1, 2
+DNS_SEC_QUESTION, DNS_SEC_ANSWER, DNS_SEC_AUTHORITY, DNS_SEC_ADDITIONAL = range(4)
+# gpk_dns (64 B): one candidate's message
+DNS_DTYPE = np.dtype([
+    ("kind", "u1"), ("err", "u1"), ("status", "u1"), ("response_code", "u1"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("hdr_off", "<u4"), ("len", "<u4"), ("id", "<u2"), ("flags2", "u1"), ("flags3", "u1"), ("qdcount", "<u2"),
+    ("ancount", "<u2"), ("nscount", "<u2"), ("arcount", "<u2"), ("nrr", "<u4"), ("reserved", "<u4"), ("rr0", "<u8"),
+    ("name0", "<u8"), ("name_bytes", "<u8")])
+# gpk_dns_rr (96 B): one question or resource record
+DNS_RR_DTYPE = np.dtype([
+    ("section", "u1"), ("reserved", "u1"), ("type", "<u2"), ("cls", "<u2"), ("data_length", "<u2"), ("ttl", "<u4"),
+    ("data_off", "<u4"), ("name_off", "<u8"), ("name_len", "<u4"), ("count", "<u4"), ("rname_off", "<u8"),
+    ("rname_len", "<u4"), ("rname2_len", "<u4"), ("rname2_off", "<u8"), ("v", "<u4", (10,))])
+
+
+class Dnss(ctypes.Structure):
+    """gpk_dnss: the outputs of gpk_dns_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("rrs", ctypes.c_void_p),
+                ("names", ctypes.c_void_p), ("rr_cap", ctypes.c_uint64), ("name_cap", ctypes.c_uint64)]
 
 
 # include/gpk_afpacket.h constants
@@ -602,6 +633,11 @@ def lib():
         "gpk_control_batch_host": ([vp, P(Batch), P(Results), u32, u32, P(Controls)], c_int),
         "gpk_controller_set_sum_threshold": ([vp, u32], c_int),
         "gpk_control_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_dns_decoder_create": ([P(vp), c_int, u64], c_int),
+        "gpk_dns_decoder_destroy": ([vp], c_int),
+        "gpk_dns_batch": ([vp, vp, vp, P(Batch), P(Results), P(Dnss), vp], c_int),
+        "gpk_dns_batch_host": ([vp, P(Batch), P(Results), P(Dnss)], c_int),
+        "gpk_dns_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

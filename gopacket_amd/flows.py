@@ -43,6 +43,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
   ControlDecoder(max_packets).decode(...)  gpk_control_batch (include/gpk_control.h): the ICMPv4,
                                            ICMPv6 (+Echo) and ARP layers of the packets whose
                                            decode stopped in front of one, and their checksums
+  DNSDecoder(max_packets).decode(...)      gpk_dns_batch (include/gpk_dns.h): the DNS messages
+                                           of the packets whose decode stopped in front of
+                                           LayerTypeDNS: message records, one entry per question
+                                           or resource record, and the decompressed names
 """
 import ctypes
 
@@ -899,16 +903,20 @@ class _PostPass(_Handle):
         """Lane group of the sums: 64 lanes from `nbytes` on, 16 below."""
         _lib.check(getattr(_lib.lib(), self._set_threshold)(self.h, int(nbytes)))
 
-    def _device(self, ctx, data, offsets, caplens, records, layouts, parser, kinds, sums, out, stream):
+    def _device_outputs(self, n, dev):
+        """The OUTPUTS arrays for n packets as device tensors: records as bytes, the rest as int32 / int64."""
         import numpy as np
         import torch
-        n, dev = offsets.numel(), offsets.device
-        if out is None:  # records as bytes, the rest as int32 / int64; the call zeroes class_start and counts
-            out = {}
-            for key, count, dt in self.OUTPUTS:
-                dt = np.dtype(dt)
-                out[key] = (torch.empty(count(n) * dt.itemsize, dtype=torch.uint8, device=dev) if dt.fields else
-                            torch.empty(count(n), dtype=torch.int64 if dt.itemsize == 8 else torch.int32, device=dev))
+        out = {}
+        for key, count, dt in self.OUTPUTS:
+            dt = np.dtype(dt)
+            out[key] = (torch.empty(count(n) * dt.itemsize, dtype=torch.uint8, device=dev) if dt.fields else
+                        torch.empty(count(n), dtype=torch.int64 if dt.itemsize == 8 else torch.int32, device=dev))
+        return out
+
+    def _device(self, ctx, data, offsets, caplens, records, layouts, parser, kinds, sums, out, stream):
+        if out is None:  # the call zeroes class_start and counts
+            out = self._device_outputs(offsets.numel(), offsets.device)
         b = _lib.Batch.of(data, offsets, caplens)
         r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
         o = self._Out(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS])
@@ -918,19 +926,25 @@ class _PostPass(_Handle):
         return out
 
     @classmethod
-    def _host(cls, data, offsets, caplens, records, layouts, parser, kinds, sums, fill):
+    def _host_arguments(cls, data, offsets, caplens, records, layouts, fill, extra=()):
+        """(out, gpk_batch, gpk_results, the input arrays they point into): the
+        OUTPUTS arrays for the batch, and `extra` (key, count, dtype) ones, all
+        starting as `fill` bytes."""
         import numpy as np
-        data = np.ascontiguousarray(data, np.uint8)
-        offsets = np.ascontiguousarray(offsets, np.uint64)
-        caplens = np.ascontiguousarray(caplens, np.uint32)
-        records = np.ascontiguousarray(records, _lib.RECORD_DTYPE)
-        layouts = np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE)
-        n = len(caplens)
-        out = {key: np.empty(count(n), dt) for key, count, dt in cls.OUTPUTS}
+        keep = (np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(offsets, np.uint64),
+                np.ascontiguousarray(caplens, np.uint32), np.ascontiguousarray(records, _lib.RECORD_DTYPE),
+                np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE))
+        n = len(keep[2])
+        out = {key: np.empty(count(n), dt) for key, count, dt in tuple(cls.OUTPUTS) + tuple(extra)}
         for a in out.values():
             a.view(np.uint8)[:] = fill
-        b = _lib.Batch(data.ctypes.data, offsets.ctypes.data, caplens.ctypes.data, n, data.size)
-        r = _lib.Results(records.ctypes.data, None, None, layouts.ctypes.data)
+        b = _lib.Batch(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, n, keep[0].size)
+        r = _lib.Results(keep[3].ctypes.data, None, None, keep[4].ctypes.data)
+        return out, b, r, keep
+
+    @classmethod
+    def _host(cls, data, offsets, caplens, records, layouts, parser, kinds, sums, fill):
+        out, b, r, _keep = cls._host_arguments(data, offsets, caplens, records, layouts, fill)
         o = cls._Out(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS])
         _lib.check(getattr(_lib.lib(), cls._batch_host)(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
                                                         cls._FLAG if sums else 0, ctypes.byref(o)))
@@ -997,3 +1011,87 @@ class ControlDecoder(_PostPass):
         """The same over numpy arrays on the calling thread
         (gpk_control_batch_host); `fill` is the byte the outputs start with."""
         return cls._host(data, offsets, caplens, records, layouts, parser, kinds, checksum, fill)
+
+
+class DNSDecoder(_PostPass):
+    """gpk_dns_batch (include/gpk_dns.h): the DNS messages at the end of a
+    decoded device batch. Owns the workspace of the scans for up to
+    max_packets packets; device=None makes a host-only one (decode_host).
+
+    The result is variable-length: records[m] (DNS_DTYPE) name ranges of
+    rrs[rr_cap] (DNS_RR_DTYPE) and of the byte arena names[name_cap]. A message
+    whose range does not fit either capacity is not written (DNS_ST_DROPPED);
+    counts tells what the batch needs (needed()), and decode_all /
+    decode_host_all size first and decode once more with exactly that."""
+
+    _create, _destroy = "gpk_dns_decoder_create", "gpk_dns_decoder_destroy"
+    _Out = _lib.Dnss
+    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
+               ("records", lambda n: n, _lib.DNS_DTYPE), ("counts", lambda n: 8, "u4"))
+    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("rrs", "names")
+
+    @staticmethod
+    def needed(counts):
+        """(entries, name bytes) the batch needs, from counts[8] (uint32)."""
+        c = [int(x) & 0xffffffff for x in counts]
+        return c[4] | c[5] << 32, c[6] | c[7] << 32
+
+    def decode(self, ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, out=None, stream=None):
+        """Device tensors in: the batch (data 16-byte aligned), and the records
+        and layouts of ctx.decode_device(parser, ...) for it. Returns
+        dict(verdict[n], class_start[3], index[n], records[64 n] (uint8,
+        _lib.DNS_DTYPE), counts[8], rrs[96 rr_cap] (uint8, _lib.DNS_RR_DTYPE),
+        names[name_cap] (uint8)) of device tensors (or fills `out`); entries at
+        and past counts[0] are not written, nor is anything past a capacity."""
+        import torch
+        rr_cap, name_cap = int(rr_cap), int(name_cap)
+        if out is None:
+            dev = offsets.device
+            out = self._device_outputs(offsets.numel(), dev)
+            out["rrs"] = torch.empty(rr_cap * _lib.DNS_RR_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            out["names"] = torch.empty(name_cap, dtype=torch.uint8, device=dev)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = _lib.Dnss(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
+                      out["rrs"].data_ptr() if rr_cap else None, out["names"].data_ptr() if name_cap else None,
+                      rr_cap, name_cap)
+        _lib.check(_lib.lib().gpk_dns_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o),
+                                            _lib.stream_ptr(stream)))
+        return out
+
+    def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, rr_cap=0, name_cap=0, stream=None):
+        """decode with capacities that hold every message: a first call with
+        rr_cap / name_cap, and, when counts reports an overflow, a second one
+        with exactly the sizes it needs. With the default capacities of 0 the
+        first call only sizes: no memory is set aside on a guess, at the price
+        of a second pass whenever the batch holds a message that decodes.
+        Synchronizes on the counts."""
+        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, stream=stream)
+        counts = out["counts"].cpu().numpy().view("u4")
+        if int(counts[3]):
+            rr_cap, name_cap = self.needed(counts)
+            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, stream=stream)
+        return out
+
+    @classmethod
+    def decode_host(cls, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_dns_batch_host); `fill` is the byte the outputs start with."""
+        rr_cap, name_cap = int(rr_cap), int(name_cap)
+        out, b, r, _keep = cls._host_arguments(
+            data, offsets, caplens, records, layouts, fill,
+            (("rrs", lambda n: rr_cap, _lib.DNS_RR_DTYPE), ("names", lambda n: name_cap, "u1")))
+        o = _lib.Dnss(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
+                      out["rrs"].ctypes.data if rr_cap else None, out["names"].ctypes.data if name_cap else None,
+                      rr_cap, name_cap)
+        _lib.check(_lib.lib().gpk_dns_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, rr_cap=0, name_cap=0):
+        """decode_host with the retry of decode_all."""
+        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rr_cap, name_cap)
+        if int(out["counts"][3]):
+            rr_cap, name_cap = cls.needed(out["counts"])
+            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rr_cap, name_cap)
+        return out

@@ -618,11 +618,14 @@ class DecodingLayerParser:
         self._dlc = dlc
         inst = dlc._instances()
         self._decoders = {k: d for k, d in inst.items()
-                          if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)}  # kind -> instance
+                          if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)
+                          and not getattr(d, "dns_kind", 0)}  # kind -> instance
         # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
         self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
         # layers.ICMPv4 / ICMPv6 / ICMPv6Echo / ARP: decoded after the six-layer decode (gpk_control_batch), by GPK_CTL_* kind
         self._controls = {d.control_kind: d for d in inst.values() if getattr(d, "control_kind", 0)}
+        # layers.DNS: decoded after the control pass (gpk_dns_batch)
+        self._dns = next((d for d in inst.values() if getattr(d, "dns_kind", 0)), None)
         self._cfg = None
 
     def AddDecodingLayer(self, d):
@@ -662,7 +665,7 @@ class DecodingLayerParser:
         """Decode one packet on the GPU; fills the registered layers and the
         `decoded` list (truncated first, as parser.go:303-317 does)."""
         batch = PacketBatch.from_packets([data])
-        if self._tunnels or self._controls:  # one packet: the host entries (gpk_tunnel_batch_host, gpk_control_batch_host)
+        if self._tunnels or self._controls or self._dns is not None:  # one packet: the host entries (gpk_*_batch_host)
             return TunnelBatchResult(self, batch, _lib.OUT_ALL, True, device=False).Hydrate(0, decoded)
         res = self.DecodeBatch(batch, layouts=True)
         return res.Hydrate(0, decoded)
@@ -684,10 +687,15 @@ class DecodingLayerParser:
         a TunnelBatchResult too: after each decode the control pass
         (gpk_control_batch) appends those layers to the packets whose decode
         stopped in front of one; checksum=True also makes their
-        VerifyChecksum on the device."""
-        if self._tunnels or self._controls:
+        VerifyChecksum on the device.
+
+        A parser that holds layers.DNS returns a TunnelBatchResult as well:
+        after the control pass the DNS pass (gpk_dns_batch) decodes the
+        message of every packet whose decode stopped in front of
+        LayerTypeDNS, on every tunnel level."""
+        if self._tunnels or self._controls or self._dns is not None:
             if fields:
-                raise ValueError("fields=True is not available for a parser with tunnel or control layers")
+                raise ValueError("fields=True is not available for a parser with tunnel, control or DNS layers")
             return TunnelBatchResult(self, batch, outputs, gre_checksum, checksum=checksum)
         cfg = self._config(outputs)
         if fields:
@@ -963,11 +971,13 @@ class TunnelPart:
     i.e. the level's own checksum and flow outputs; peel: gpk_tunnel_batch's
     outputs for it (host arrays), the tunnel headers found at its end;
     control: gpk_control_batch's outputs for it (host arrays), or None when
-    the parser holds no control layer."""
+    the parser holds no control layer; dns: gpk_dns_batch's outputs for it
+    (host arrays: records, rrs and names cut to what was written), or None
+    when the parser holds no layers.DNS."""
 
-    def __init__(self, first, index, batch, result, peel, control=None):
+    def __init__(self, first, index, batch, result, peel, control=None, dns=None):
         self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
-        self.control = control
+        self.control, self.dns = control, dns
 
 
 class TunnelBatchResult:
@@ -993,7 +1003,7 @@ class TunnelBatchResult:
     def _clone(self, first):
         import copy
         p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
-        p.first, p._tunnels, p._controls, p._cfg = LayerType(first), {}, {}, None
+        p.first, p._tunnels, p._controls, p._dns, p._cfg = LayerType(first), {}, {}, None, None
         return p
 
     @staticmethod
@@ -1003,12 +1013,12 @@ class TunnelBatchResult:
                     counts=np.zeros(8, np.uint32), index=np.zeros(0, np.uint32), in_offsets=np.zeros(0, np.uint64),
                     in_caplens=np.zeros(0, np.uint32), tunnels=np.zeros(0, _lib.TUNNEL_DTYPE))
 
-    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None):
+    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None):
         if len(self.levels) <= level:
             self.levels.append([])
         p = self._clone(first)
         part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
-                          BatchResult(p, None, r), peel, control)
+                          BatchResult(p, None, r), peel, control, dns)
         part.result.batch = part.batch
         self.levels[level].append(part)
         for pos, g in enumerate(index):
@@ -1034,7 +1044,7 @@ class TunnelBatchResult:
         return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
 
     def _run_host(self, outputs, kinds, gre_checksum):
-        from .flows import ControlDecoder, Detunneler
+        from .flows import ControlDecoder, Detunneler, DNSDecoder
         b = self.batch
         work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
         level = 0
@@ -1049,14 +1059,16 @@ class TunnelBatchResult:
                     if kinds else self._no_peel(len(index))
                 ctl = ControlDecoder.decode_host(b.data, offs, caps, r["records"], r["layouts"], cfg, self._ctl_kinds,
                                                  self._ctl_checksum) if self._ctl_kinds else None
-                part = self._add_part(level, first, index, offs, caps, r, pl, ctl)
+                dns = DNSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
+                    if self.parser._dns is not None else None
+                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns)
                 for lt, js in self._next_work(part, level):
                     nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
             work, level = nxt, level + 1
 
     def _run_device(self, outputs, kinds, gre_checksum):
         import torch
-        from .flows import ControlDecoder, Detunneler
+        from .flows import ControlDecoder, Detunneler, DNSDecoder
         b = self.batch
         ctx = self.parser.ctx()
         dev = torch.device("cuda", ctx.device)
@@ -1065,6 +1077,7 @@ class TunnelBatchResult:
         data = torch.from_numpy(host).to(dev)
         det = Detunneler(max(len(b), 1), ctx.device) if kinds else None
         ctd = ControlDecoder(max(len(b), 1), ctx.device) if self._ctl_kinds else None
+        dnd = DNSDecoder(max(len(b), 1), ctx.device) if self.parser._dns is not None else None
         try:
             work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
                      torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
@@ -1083,6 +1096,7 @@ class TunnelBatchResult:
                     out = det.peel(ctx, data, offs, caps, rec, lay, cfg, kinds, gre_checksum) if det else None
                     cout = ctd.decode(ctx, data, offs, caps, rec, lay, cfg, self._ctl_kinds, self._ctl_checksum) \
                         if ctd else None
+                    dout = dnd.decode_all(ctx, data, offs, caps, rec, lay, cfg) if dnd else None
                     torch.cuda.synchronize(dev)
                     r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
                              err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
@@ -1096,9 +1110,21 @@ class TunnelBatchResult:
                                    index=cout["index"][:cm].cpu().numpy().view(np.uint32),
                                    records=cout["records"][:cm * _lib.CONTROL_DTYPE.itemsize].cpu().numpy().view(
                                        _lib.CONTROL_DTYPE))
+                    dns = None
+                    if dout is not None:
+                        dc = dout["counts"].cpu().numpy().view(np.uint32)
+                        need_rr, need_nb = DNSDecoder.needed(dc)
+                        dns = dict(verdict=dout["verdict"].cpu().numpy(),
+                                   class_start=dout["class_start"].cpu().numpy().view(np.uint32), counts=dc,
+                                   index=dout["index"][:int(dc[0])].cpu().numpy().view(np.uint32),
+                                   records=dout["records"][:int(dc[0]) * _lib.DNS_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.DNS_DTYPE),
+                                   rrs=dout["rrs"][:need_rr * _lib.DNS_RR_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.DNS_RR_DTYPE),
+                                   names=dout["names"][:need_nb].cpu().numpy())
                     if out is None:
                         self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl)
+                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns)
                         continue
                     m = int(out["counts"][0].item())
                     pl = dict(verdict=out["verdict"].cpu().numpy(),
@@ -1110,7 +1136,7 @@ class TunnelBatchResult:
                               tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
                                   _lib.TUNNEL_DTYPE))
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl)
+                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns)
                     for lt, js in self._next_work(part, level):
                         if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
                             io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
@@ -1120,7 +1146,7 @@ class TunnelBatchResult:
                         nxt.append((lt, index[pl["index"][js]], io, ic))
                 work, level = nxt, level + 1
         finally:
-            for h in (det, ctd):
+            for h in (det, ctd, dnd):
                 if h is not None:
                     h.close()
 
@@ -1142,6 +1168,24 @@ class TunnelBatchResult:
         v = int(part.control["verdict"][pos])
         return part.control["records"][v] if v >= 0 else None
 
+    def _dns(self, part, pos):
+        """The gpk_dns record of a part's packet, or None: not a candidate."""
+        if part.dns is None:
+            return None
+        v = int(part.dns["verdict"][pos])
+        return part.dns["records"][v] if v >= 0 else None
+
+    def DNS(self, i):
+        """(the gpk_dns record (DNS_DTYPE), its gpk_dns_rr entries (DNS_RR_DTYPE),
+        the name arena) of packet i, or None: not a candidate. A failed
+        message has no entries."""
+        part, pos = self._chain[i][-1]
+        t = self._dns(part, pos)
+        if t is None:
+            return None
+        r0 = int(t["rr0"])
+        return t, part.dns["rrs"][r0:r0 + int(t["nrr"])], part.dns["names"]
+
     def Control(self, i):
         """The gpk_control record (CONTROL_DTYPE) of packet i, or None."""
         return self._control(*self._chain[i][-1])
@@ -1156,6 +1200,9 @@ class TunnelBatchResult:
             c = self._control(part, pos)
             if c is not None:
                 out += [LayerType(int(x)) for x in c["layer_types"][:int(c["nlayers"])]]
+            d = self._dns(part, pos)
+            if d is not None and not int(d["err"]):
+                out.append(LayerType(_lib.LT_DNS))
         return out
 
     def Truncated(self, i):
@@ -1163,8 +1210,10 @@ class TunnelBatchResult:
         for part, pos in self._chain[i]:
             t = self._tunnel(part, pos)
             c = self._control(part, pos)
+            d = self._dns(part, pos)
             tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED)) \
-                or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED))
+                or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED)) \
+                or (d is not None and bool(int(d["status"]) & _lib.DNS_ST_TRUNCATED))
         return tr
 
     def Err(self, i):
@@ -1173,6 +1222,13 @@ class TunnelBatchResult:
         part, pos = self._chain[i][-1]
         t = self._tunnel(part, pos)
         c = self._control(part, pos)
+        d = self._dns(part, pos)
+        if d is not None:  # DNS has no payload: its error, or nil (dns.go:434-436)
+            if int(d["err"]):
+                buf = ctypes.create_string_buffer(256)
+                _lib.lib().gpk_dns_format_error(int(d["err"]), int(d["err_a0"]), int(d["err_a1"]), buf, 256)
+                return GoError(buf.value.decode())
+            return None
         if c is not None:  # the control layers' loop ended the decode: its error, the type it returned, or nil
             if int(c["err"]):
                 buf = ctypes.create_string_buffer(256)
@@ -1220,6 +1276,10 @@ class TunnelBatchResult:
                 elif int(c["nlayers"]) > 1:  # gopacket.Payload
                     o = int(c["payload_off"])
                     p._decoders[_lib.DEC_PAYLOAD]._hydrate(pkt[o:o + int(c["payload_len"])])
+            d = self._dns(part, pos)
+            if d is not None and not int(d["err"]):
+                r0 = int(d["rr0"])
+                p._dns._from_record(d, part.dns["rrs"][r0:r0 + int(d["nrr"])], part.dns["names"], part.batch.packet(pos))
         decoded[:] = self.Decoded(i)
         p.Truncated = self.Truncated(i)
         return self.Err(i)

@@ -5,7 +5,9 @@ layers GRE, VXLAN, Geneve (layers/{gre,vxlan,geneve}.go), which are filled from
 the gpk_tunnel record of gpk_tunnel_batch (include/gpk_tunnel.h), and the four
 control layers ICMPv4, ICMPv6, ICMPv6Echo, ARP (layers/{icmp4,icmp6,icmp6msg,
 arp}.go), filled from the gpk_control record of gpk_control_batch
-(include/gpk_control.h).
+(include/gpk_control.h), and DNS (layers/dns.go), filled from the gpk_dns
+record, the gpk_dns_rr entries and the name arena of gpk_dns_batch
+(include/gpk_dns.h).
 
 These structs are filled from device results, in one of two ways:
 - _fill(pkt, s, e, f): from the gpk_fields record the device wrote for the
@@ -1545,3 +1547,263 @@ class ARP(_ControlLayer):
         self.SourceHwAddress, self.SourceProtAddress = pkt[a:a + hw], pkt[a + hw:a + hw + pr]
         self.DstHwAddress, self.DstProtAddress = pkt[a + hw + pr:a + 2 * hw + pr], pkt[a + 2 * hw + pr:h + c]
         self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["payload_len"])]
+
+
+# ---- layers/dns.go ------------------------------------------------------------------
+# A DecodingLayerParser that holds layers.DNS decodes the messages on the device
+# after the six-layer decode and the control pass (gpk_dns_batch); the struct is
+# filled from the packet's gpk_dns record, its gpk_dns_rr entries, the name arena
+# and the packet's bytes (_from_record).
+class DNSClass(int):
+    pass
+
+
+class DNSType(int):
+    pass
+
+
+class DNSOpCode(int):
+    pass
+
+
+class DNSResponseCode(int):
+    pass
+
+
+DNSClassIN, DNSClassCS, DNSClassCH, DNSClassHS, DNSClassAny = (DNSClass(x) for x in (1, 2, 3, 4, 255))
+(DNSTypeA, DNSTypeNS, DNSTypeMD, DNSTypeMF, DNSTypeCNAME, DNSTypeSOA, DNSTypeMB, DNSTypeMG, DNSTypeMR, DNSTypeNULL,
+ DNSTypeWKS, DNSTypePTR, DNSTypeHINFO, DNSTypeMINFO, DNSTypeMX, DNSTypeTXT) = (DNSType(x) for x in range(1, 17))
+(DNSTypeAAAA, DNSTypeSRV, DNSTypeNAPTR, DNSTypeOPT, DNSTypeRRSIG, DNSTypeDNSKEY, DNSTypeSVCB, DNSTypeHTTPS,
+ DNSTypeURI) = (DNSType(x) for x in (28, 33, 35, 41, 46, 48, 64, 65, 256))
+(DNSOpCodeQuery, DNSOpCodeIQuery, DNSOpCodeStatus, DNSOpCodeNotify, DNSOpCodeUpdate) = (
+    DNSOpCode(x) for x in (0, 1, 2, 4, 5))
+(DNSResponseCodeNoErr, DNSResponseCodeFormErr, DNSResponseCodeServFail, DNSResponseCodeNXDomain,
+ DNSResponseCodeNotImp, DNSResponseCodeRefused, DNSResponseCodeYXDomain, DNSResponseCodeYXRRSet,
+ DNSResponseCodeNXRRSet, DNSResponseCodeNotAuth, DNSResponseCodeNotZone) = (DNSResponseCode(x) for x in range(11))
+(DNSResponseCodeBadVers, DNSResponseCodeBadSig, DNSResponseCodeBadKey, DNSResponseCodeBadTime,
+ DNSResponseCodeBadMode, DNSResponseCodeBadName, DNSResponseCodeBadAlg, DNSResponseCodeBadTruc,
+ DNSResponseCodeBadCookie) = (DNSResponseCode(x) for x in (16, 16, 17, 18, 19, 20, 21, 22, 23))
+
+
+@dataclass
+class DNSQuestion:
+    Name: bytes = b""
+    Type: DNSType = DNSType(0)
+    Class: DNSClass = DNSClass(0)
+
+
+@dataclass
+class DNSSOA:
+    MName: bytes = b""
+    RName: bytes = b""
+    Serial: int = 0
+    Refresh: int = 0
+    Retry: int = 0
+    Expire: int = 0
+    Minimum: int = 0
+
+
+@dataclass
+class DNSSRV:
+    Priority: int = 0
+    Weight: int = 0
+    Port: int = 0
+    Name: bytes = b""
+
+
+@dataclass
+class DNSMX:
+    Preference: int = 0
+    Name: bytes = b""
+
+
+@dataclass
+class DNSURI:
+    Priority: int = 0
+    Weight: int = 0
+    Target: bytes = b""
+
+
+@dataclass
+class DNSNAPTR:
+    Order: int = 0
+    Preference: int = 0
+    Flags: bytes = b""
+    Service: bytes = b""
+    Regexp: bytes = b""
+    Replacement: bytes = b""
+
+
+@dataclass
+class DNSOPT:
+    Code: int = 0
+    Data: bytes = b""
+
+
+@dataclass
+class DNSSvcParam:
+    Key: int = 0
+    Value: bytes = b""
+
+
+@dataclass
+class DNSSVCB:
+    Priority: int = 0
+    Target: bytes = b""
+    Params: list = field(default_factory=list)
+
+
+@dataclass
+class DNSRRSIG:
+    TypeCovered: DNSType = DNSType(0)
+    Algorithm: int = 0
+    Labels: int = 0
+    OriginalTTL: int = 0
+    Expiration: int = 0
+    Inception: int = 0
+    KeyTag: int = 0
+    SignerName: bytes = b""
+    Signature: bytes = b""
+
+
+@dataclass
+class DNSKEY:
+    Flags: int = 0
+    Protocol: int = 0
+    Algorithm: int = 0
+    PublicKey: bytes = b""
+
+
+@dataclass
+class DNSResourceRecord:
+    Name: bytes = b""
+    Type: DNSType = DNSType(0)
+    Class: DNSClass = DNSClass(0)
+    TTL: int = 0
+    DataLength: int = 0
+    Data: bytes = b""
+    IP: bytes = b""
+    NS: bytes = b""
+    CNAME: bytes = b""
+    PTR: bytes = b""
+    TXTs: list = field(default_factory=list)
+    SOA: DNSSOA = field(default_factory=DNSSOA)
+    SRV: DNSSRV = field(default_factory=DNSSRV)
+    MX: DNSMX = field(default_factory=DNSMX)
+    NAPTR: DNSNAPTR = field(default_factory=DNSNAPTR)
+    OPT: list = field(default_factory=list)
+    RRSIG: DNSRRSIG = field(default_factory=DNSRRSIG)
+    DNSKEY: DNSKEY = field(default_factory=DNSKEY)
+    SVCB: DNSSVCB = field(default_factory=DNSSVCB)
+    URI: DNSURI = field(default_factory=DNSURI)
+    TXT: bytes = b""
+
+
+def _dns_entry(r, names, pkt):
+    """A DNSQuestion or DNSResourceRecord from a gpk_dns_rr entry, the name
+    arena and the packet. The lists (TXTs, OPT, SvcParams) are sliced out of
+    the packet with the walk the device has validated (r["count"] items)."""
+    def arena(off, ln):
+        o = int(r[off])
+        return bytes(names[o:o + int(r[ln])])
+    name = arena("name_off", "name_len")
+    typ = int(r["type"])
+    if int(r["section"]) == _lib.DNS_SEC_QUESTION:
+        return DNSQuestion(name, DNSType(typ), DNSClass(int(r["cls"])))
+    d, dl = int(r["data_off"]), int(r["data_length"])
+    data = bytes(pkt[d:d + dl])
+    rr = DNSResourceRecord(name, DNSType(typ), DNSClass(int(r["cls"])), int(r["ttl"]), dl, data)
+    if not dl:  # dns.go:1080: decodeRData is skipped
+        return rr
+    v = [int(x) for x in r["v"]]
+    rname = arena("rname_off", "rname_len")
+
+    def items(at, width):  # `count` items of a `width`-byte length field behind a (width - 1) * 2-byte code
+        out, head = [], 2 * (width - 1)
+        for _ in range(int(r["count"])):
+            ln = int.from_bytes(pkt[at + head:at + head + width], "big")
+            out.append((int.from_bytes(pkt[at:at + head], "big"), bytes(pkt[at + head + width:at + head + width + ln])))
+            at += head + width + ln
+        return out
+    if typ in (1, 28):
+        rr.IP = data
+    elif typ in (16, 13):
+        rr.TXT = data
+        rr.TXTs = [x for _, x in items(d, 1)]
+    elif typ == 2:
+        rr.NS = rname
+    elif typ == 5:
+        rr.CNAME = rname
+    elif typ == 12:
+        rr.PTR = rname
+    elif typ == 6:
+        rr.SOA = DNSSOA(rname, arena("rname2_off", "rname2_len"), *v[:5])
+    elif typ == 15:
+        rr.MX = DNSMX(v[0], rname)
+    elif typ == 256:
+        rr.URI = DNSURI(v[0], v[1], data[4:])
+    elif typ == 33:
+        rr.SRV = DNSSRV(v[0], v[1], v[2], rname)
+    elif typ == 35:
+        rr.NAPTR = DNSNAPTR(v[0], v[1], bytes(pkt[v[2]:v[2] + v[3]]), bytes(pkt[v[4]:v[4] + v[5]]),
+                            bytes(pkt[v[6]:v[6] + v[7]]), rname)
+    elif typ == 41:
+        rr.OPT = [DNSOPT(c, x) for c, x in items(d, 2)]
+    elif typ == 46:
+        rr.RRSIG = DNSRRSIG(DNSType(v[0]), v[1], v[2], v[3], v[4], v[5], v[6], rname, bytes(pkt[v[7]:v[7] + v[8]]))
+    elif typ == 48:
+        rr.DNSKEY = DNSKEY(v[0], v[1], v[2], data[4:])
+    elif typ in (64, 65):
+        rr.SVCB = DNSSVCB(v[0], rname, [DNSSvcParam(k, x) for k, x in items(v[1], 2)])
+    return rr
+
+
+class DNS(BaseLayer):
+    """dns.go:284-436. Payload() is nil: nothing follows a DNS layer."""
+    kind = 300
+    dns_kind = _lib.DNS_KIND
+
+    def __init__(self):
+        self._reset()
+
+    def _reset(self):
+        self.ID = 0
+        self.QR = self.AA = self.TC = self.RD = self.RA = False
+        self.OpCode = DNSOpCode(0)
+        self.Z = 0
+        self.ResponseCode = DNSResponseCode(0)
+        self.QDCount = self.ANCount = self.NSCount = self.ARCount = 0
+        self.Questions, self.Answers, self.Authorities, self.Additionals = [], [], [], []
+        self.Contents = self.Payload = b""
+
+    def LayerType(self):
+        return LayerTypeDNS
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeDNS])
+
+    def NextLayerType(self):
+        return LayerTypePayload
+
+    def LayerPayload(self):
+        return b""
+
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("DNS decodes through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+    def _from_record(self, t, rrs, names, pkt):
+        """t: the gpk_dns record (decoded, not dropped); rrs: its entries; names: the arena."""
+        self._reset()
+        f2, f3 = int(t["flags2"]), int(t["flags3"])
+        self.ID = int(t["id"])
+        self.QR, self.OpCode = bool(f2 & 0x80), DNSOpCode(f2 >> 3 & 0xF)
+        self.AA, self.TC, self.RD, self.RA = bool(f2 & 4), bool(f2 & 2), bool(f2 & 1), bool(f3 & 0x80)
+        self.Z = f3 >> 4 & 7
+        self.ResponseCode = DNSResponseCode(int(t["response_code"]))
+        self.QDCount, self.ANCount = int(t["qdcount"]), int(t["ancount"])
+        self.NSCount, self.ARCount = int(t["nscount"]), int(t["arcount"])
+        h = int(t["hdr_off"])
+        self.Contents = bytes(pkt[h:h + int(t["len"])])
+        sections = (self.Questions, self.Answers, self.Authorities, self.Additionals)
+        for r in rrs:
+            sections[int(r["section"])].append(_dns_entry(r, names, pkt))
