@@ -121,6 +121,8 @@ EXPORTS = (
     "gpk_controller_set_sum_threshold", "gpk_control_format_error",
     # include/gpk_dns.h
     "gpk_dns_decoder_create", "gpk_dns_decoder_destroy", "gpk_dns_batch", "gpk_dns_batch_host", "gpk_dns_format_error",
+    # include/gpk_tls.h
+    "gpk_tls_decoder_create", "gpk_tls_decoder_destroy", "gpk_tls_batch", "gpk_tls_batch_host", "gpk_tls_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -342,6 +344,43 @@ class Dnss(ctypes.Structure):
     _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
                 ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("rrs", ctypes.c_void_p),
                 ("names", ctypes.c_void_p), ("rr_cap", ctypes.c_uint64), ("name_cap", ctypes.c_uint64)]
+
+
+# include/gpk_tls.h constants
+LT_TLS = 140
+TLS_KIND, TLS_ALL = 1, 1
+TLS_NONE, TLS_UNKNOWN = -1, -2
+TLS_CLASS_OK, TLS_CLASS_FAILED = range(2)
+TLS_NCLASS = 2
+TLS_ERR_FIRST, TLS_ERR_END = 121, 133  # gpk_tls_err: GPK_TLS_ERR_RECORD_SHORT .. GPK_TLS_ERR_HELLO_EXTENSIONS
+TLS_ST_TRUNCATED, TLS_ST_DROPPED = 1, 2
+TLS_HS_NONE, TLS_HS_ENCRYPTED, TLS_HS_CLIENT_HELLO, TLS_HS_CLIENT_KEY = range(4)
+TLS_NO_HELLO = 0xFFFFFFFF
+ERR_PANIC_SLICE_B = 4  # gpk.h: the one panic form of the TLS path
+# gpk_tls (80 B): one candidate's message
+TLS_DTYPE = np.dtype([
+    ("err", "u1"), ("status", "u1"), ("reserved", "<u2"), ("err_a0", "<u4"), ("err_a1", "<u4"), ("hdr_off", "<u4"),
+    ("len", "<u4"), ("nrec", "<u4"), ("nccs", "<u4"), ("nalert", "<u4"), ("nhandshake", "<u4"), ("nappdata", "<u4"),
+    ("nhello", "<u4"), ("reserved2", "<u4"), ("sni_bytes", "<u8"), ("rec0", "<u8"), ("hello0", "<u8"), ("sni0", "<u8")])
+# gpk_tls_rec (16 B): one TLS record
+TLS_REC_DTYPE = np.dtype([
+    ("content_type", "u1"), ("hs", "u1"), ("v0", "u1"), ("v1", "u1"), ("version", "<u2"), ("length", "<u2"),
+    ("body_off", "<u4"), ("hello", "<u4")])
+# gpk_tls_hello (64 B): one decoded ClientHello
+TLS_HELLO_DTYPE = np.dtype([
+    ("handshake_type", "u1"), ("session_id_length", "u1"), ("compression_methods_length", "u1"), ("has_sni", "u1"),
+    ("length", "<u4"), ("protocol_version", "<u2"), ("cipher_suits_length", "<u2"), ("extensions_length", "<u2"),
+    ("reserved", "<u2"), ("packet", "<u4"), ("random_off", "<u4"), ("session_id_off", "<u4"),
+    ("cipher_suits_off", "<u4"), ("compression_methods_off", "<u4"), ("extensions_off", "<u4"), ("sni_off", "<u4"),
+    ("sni_len", "<u4"), ("sni_pos", "<u8"), ("reserved2", "<u8")])
+
+
+class Tlss(ctypes.Structure):
+    """gpk_tlss: the outputs of gpk_tls_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("recs", ctypes.c_void_p),
+                ("hellos", ctypes.c_void_p), ("snis", ctypes.c_void_p), ("rec_cap", ctypes.c_uint64),
+                ("hello_cap", ctypes.c_uint64), ("sni_cap", ctypes.c_uint64)]
 
 
 # include/gpk_afpacket.h constants
@@ -638,6 +677,11 @@ def lib():
         "gpk_dns_batch": ([vp, vp, vp, P(Batch), P(Results), P(Dnss), vp], c_int),
         "gpk_dns_batch_host": ([vp, P(Batch), P(Results), P(Dnss)], c_int),
         "gpk_dns_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_tls_decoder_create": ([P(vp), c_int, u64], c_int),
+        "gpk_tls_decoder_destroy": ([vp], c_int),
+        "gpk_tls_batch": ([vp, vp, vp, P(Batch), P(Results), P(Tlss), vp], c_int),
+        "gpk_tls_batch_host": ([vp, P(Batch), P(Results), P(Tlss)], c_int),
+        "gpk_tls_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

@@ -47,6 +47,10 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            of the packets whose decode stopped in front of
                                            LayerTypeDNS: message records, one entry per question
                                            or resource record, and the decompressed names
+  TLSDecoder(max_packets).decode(...)      gpk_tls_batch (include/gpk_tls.h): the TLS messages
+                                           of the packets whose decode stopped in front of
+                                           LayerTypeTLS: message records, one entry per TLS
+                                           record and per ClientHello, and the server names
 """
 import ctypes
 
@@ -1094,4 +1098,94 @@ class DNSDecoder(_PostPass):
         if int(out["counts"][3]):
             rr_cap, name_cap = cls.needed(out["counts"])
             out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rr_cap, name_cap)
+        return out
+
+
+class TLSDecoder(_PostPass):
+    """gpk_tls_batch (include/gpk_tls.h): the TLS messages at the end of a
+    decoded device batch. Owns the workspace of the scans for up to
+    max_packets packets; device=None makes a host-only one (decode_host).
+
+    The result is variable-length: records[m] (TLS_DTYPE) name ranges of
+    recs[rec_cap] (TLS_REC_DTYPE, one per TLS record), of hellos[hello_cap]
+    (TLS_HELLO_DTYPE, one per decoded ClientHello) and of the byte arena
+    snis[sni_cap] (the server names). A message whose range does not fit every
+    capacity is not written (TLS_ST_DROPPED); counts tells what the batch
+    needs (needed()), and decode_all / decode_host_all size first and decode
+    once more with exactly that."""
+
+    _create, _destroy = "gpk_tls_decoder_create", "gpk_tls_decoder_destroy"
+    _Out = _lib.Tlss
+    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
+               ("records", lambda n: n, _lib.TLS_DTYPE), ("counts", lambda n: 12, "u4"))
+    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("recs", "hellos", "snis")
+
+    @staticmethod
+    def needed(counts):
+        """(record entries, hello entries, server name bytes) the batch needs, from counts[12] (uint32)."""
+        c = [int(x) & 0xffffffff for x in counts]
+        return c[4] | c[5] << 32, c[6] | c[7] << 32, c[8] | c[9] << 32
+
+    def decode(self, ctx, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap, out=None,
+               stream=None):
+        """Device tensors in: the batch (data 16-byte aligned), and the records
+        and layouts of ctx.decode_device(parser, ...) for it. Returns
+        dict(verdict[n], class_start[3], index[n], records[80 n] (uint8,
+        _lib.TLS_DTYPE), counts[12], recs[16 rec_cap] (uint8,
+        _lib.TLS_REC_DTYPE), hellos[64 hello_cap] (uint8,
+        _lib.TLS_HELLO_DTYPE), snis[sni_cap] (uint8)) of device tensors (or
+        fills `out`); entries at and past counts[0] are not written, nor is
+        anything past a capacity."""
+        import torch
+        rec_cap, hello_cap, sni_cap = int(rec_cap), int(hello_cap), int(sni_cap)
+        if out is None:
+            dev = offsets.device
+            out = self._device_outputs(offsets.numel(), dev)
+            out["recs"] = torch.empty(rec_cap * _lib.TLS_REC_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            out["hellos"] = torch.empty(hello_cap * _lib.TLS_HELLO_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+            out["snis"] = torch.empty(sni_cap, dtype=torch.uint8, device=dev)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = _lib.Tlss(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
+                      out["recs"].data_ptr() if rec_cap else None, out["hellos"].data_ptr() if hello_cap else None,
+                      out["snis"].data_ptr() if sni_cap else None, rec_cap, hello_cap, sni_cap)
+        _lib.check(_lib.lib().gpk_tls_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o),
+                                            _lib.stream_ptr(stream)))
+        return out
+
+    def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, rec_cap=0, hello_cap=0, sni_cap=0,
+                   stream=None):
+        """decode with capacities that hold every message: a first call with
+        the capacities given, and, when counts reports an overflow, a second
+        one with exactly the sizes it needs. With the default capacities of 0
+        the first call only sizes. Synchronizes on the counts."""
+        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap,
+                          stream=stream)
+        counts = out["counts"].cpu().numpy().view("u4")
+        if int(counts[3]):
+            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, *self.needed(counts),
+                              stream=stream)
+        return out
+
+    @classmethod
+    def decode_host(cls, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_tls_batch_host); `fill` is the byte the outputs start with."""
+        rec_cap, hello_cap, sni_cap = int(rec_cap), int(hello_cap), int(sni_cap)
+        out, b, r, _keep = cls._host_arguments(
+            data, offsets, caplens, records, layouts, fill,
+            (("recs", lambda n: rec_cap, _lib.TLS_REC_DTYPE), ("hellos", lambda n: hello_cap, _lib.TLS_HELLO_DTYPE),
+             ("snis", lambda n: sni_cap, "u1")))
+        o = _lib.Tlss(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
+                      out["recs"].ctypes.data if rec_cap else None, out["hellos"].ctypes.data if hello_cap else None,
+                      out["snis"].ctypes.data if sni_cap else None, rec_cap, hello_cap, sni_cap)
+        _lib.check(_lib.lib().gpk_tls_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, rec_cap=0, hello_cap=0, sni_cap=0):
+        """decode_host with the retry of decode_all."""
+        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap)
+        if int(out["counts"][3]):
+            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, *cls.needed(out["counts"]))
         return out

@@ -619,13 +619,15 @@ class DecodingLayerParser:
         inst = dlc._instances()
         self._decoders = {k: d for k, d in inst.items()
                           if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)
-                          and not getattr(d, "dns_kind", 0)}  # kind -> instance
+                          and not getattr(d, "dns_kind", 0) and not getattr(d, "tls_kind", 0)}  # kind -> instance
         # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
         self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
         # layers.ICMPv4 / ICMPv6 / ICMPv6Echo / ARP: decoded after the six-layer decode (gpk_control_batch), by GPK_CTL_* kind
         self._controls = {d.control_kind: d for d in inst.values() if getattr(d, "control_kind", 0)}
         # layers.DNS: decoded after the control pass (gpk_dns_batch)
         self._dns = next((d for d in inst.values() if getattr(d, "dns_kind", 0)), None)
+        # layers.TLS: decoded after the DNS pass (gpk_tls_batch)
+        self._tls = next((d for d in inst.values() if getattr(d, "tls_kind", 0)), None)
         self._cfg = None
 
     def AddDecodingLayer(self, d):
@@ -661,11 +663,15 @@ class DecodingLayerParser:
     def ctx(self):
         return self._ctx or _default_ctx()
 
+    def _post_passes(self):
+        """Whether the parser holds a tunnel, control, DNS or TLS layer: DecodeBatch returns a TunnelBatchResult."""
+        return bool(self._tunnels or self._controls or self._dns is not None or self._tls is not None)
+
     def DecodeLayers(self, data, decoded):
         """Decode one packet on the GPU; fills the registered layers and the
         `decoded` list (truncated first, as parser.go:303-317 does)."""
         batch = PacketBatch.from_packets([data])
-        if self._tunnels or self._controls or self._dns is not None:  # one packet: the host entries (gpk_*_batch_host)
+        if self._post_passes():  # one packet: the host entries (gpk_*_batch_host)
             return TunnelBatchResult(self, batch, _lib.OUT_ALL, True, device=False).Hydrate(0, decoded)
         res = self.DecodeBatch(batch, layouts=True)
         return res.Hydrate(0, decoded)
@@ -692,10 +698,15 @@ class DecodingLayerParser:
         A parser that holds layers.DNS returns a TunnelBatchResult as well:
         after the control pass the DNS pass (gpk_dns_batch) decodes the
         message of every packet whose decode stopped in front of
-        LayerTypeDNS, on every tunnel level."""
-        if self._tunnels or self._controls or self._dns is not None:
+        LayerTypeDNS, on every tunnel level.
+
+        A parser that holds layers.TLS does too: after the DNS pass the TLS
+        pass (gpk_tls_batch) decodes the records, and the ClientHello with its
+        server name, of every packet whose decode stopped in front of
+        LayerTypeTLS, on every tunnel level (TLS(i), SNIs())."""
+        if self._post_passes():
             if fields:
-                raise ValueError("fields=True is not available for a parser with tunnel, control or DNS layers")
+                raise ValueError("fields=True is not available for a parser with tunnel, control, DNS or TLS layers")
             return TunnelBatchResult(self, batch, outputs, gre_checksum, checksum=checksum)
         cfg = self._config(outputs)
         if fields:
@@ -973,11 +984,13 @@ class TunnelPart:
     control: gpk_control_batch's outputs for it (host arrays), or None when
     the parser holds no control layer; dns: gpk_dns_batch's outputs for it
     (host arrays: records, rrs and names cut to what was written), or None
-    when the parser holds no layers.DNS."""
+    when the parser holds no layers.DNS; tls: gpk_tls_batch's outputs for it
+    (host arrays: records, recs, hellos and snis cut to what was written), or
+    None when the parser holds no layers.TLS."""
 
-    def __init__(self, first, index, batch, result, peel, control=None, dns=None):
+    def __init__(self, first, index, batch, result, peel, control=None, dns=None, tls=None):
         self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
-        self.control, self.dns = control, dns
+        self.control, self.dns, self.tls = control, dns, tls
 
 
 class TunnelBatchResult:
@@ -1003,7 +1016,7 @@ class TunnelBatchResult:
     def _clone(self, first):
         import copy
         p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
-        p.first, p._tunnels, p._controls, p._dns, p._cfg = LayerType(first), {}, {}, None, None
+        p.first, p._tunnels, p._controls, p._dns, p._tls, p._cfg = LayerType(first), {}, {}, None, None, None
         return p
 
     @staticmethod
@@ -1013,12 +1026,12 @@ class TunnelBatchResult:
                     counts=np.zeros(8, np.uint32), index=np.zeros(0, np.uint32), in_offsets=np.zeros(0, np.uint64),
                     in_caplens=np.zeros(0, np.uint32), tunnels=np.zeros(0, _lib.TUNNEL_DTYPE))
 
-    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None):
+    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None, tls=None):
         if len(self.levels) <= level:
             self.levels.append([])
         p = self._clone(first)
         part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
-                          BatchResult(p, None, r), peel, control, dns)
+                          BatchResult(p, None, r), peel, control, dns, tls)
         part.result.batch = part.batch
         self.levels[level].append(part)
         for pos, g in enumerate(index):
@@ -1044,7 +1057,7 @@ class TunnelBatchResult:
         return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
 
     def _run_host(self, outputs, kinds, gre_checksum):
-        from .flows import ControlDecoder, Detunneler, DNSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, TLSDecoder
         b = self.batch
         work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
         level = 0
@@ -1061,14 +1074,16 @@ class TunnelBatchResult:
                                                  self._ctl_checksum) if self._ctl_kinds else None
                 dns = DNSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
                     if self.parser._dns is not None else None
-                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns)
+                tls = TLSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
+                    if self.parser._tls is not None else None
+                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns, tls)
                 for lt, js in self._next_work(part, level):
                     nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
             work, level = nxt, level + 1
 
     def _run_device(self, outputs, kinds, gre_checksum):
         import torch
-        from .flows import ControlDecoder, Detunneler, DNSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, TLSDecoder
         b = self.batch
         ctx = self.parser.ctx()
         dev = torch.device("cuda", ctx.device)
@@ -1078,6 +1093,7 @@ class TunnelBatchResult:
         det = Detunneler(max(len(b), 1), ctx.device) if kinds else None
         ctd = ControlDecoder(max(len(b), 1), ctx.device) if self._ctl_kinds else None
         dnd = DNSDecoder(max(len(b), 1), ctx.device) if self.parser._dns is not None else None
+        tld = TLSDecoder(max(len(b), 1), ctx.device) if self.parser._tls is not None else None
         try:
             work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
                      torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
@@ -1097,6 +1113,7 @@ class TunnelBatchResult:
                     cout = ctd.decode(ctx, data, offs, caps, rec, lay, cfg, self._ctl_kinds, self._ctl_checksum) \
                         if ctd else None
                     dout = dnd.decode_all(ctx, data, offs, caps, rec, lay, cfg) if dnd else None
+                    tout = tld.decode_all(ctx, data, offs, caps, rec, lay, cfg) if tld else None
                     torch.cuda.synchronize(dev)
                     r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
                              err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
@@ -1122,9 +1139,23 @@ class TunnelBatchResult:
                                    rrs=dout["rrs"][:need_rr * _lib.DNS_RR_DTYPE.itemsize].cpu().numpy().view(
                                        _lib.DNS_RR_DTYPE),
                                    names=dout["names"][:need_nb].cpu().numpy())
+                    tls = None
+                    if tout is not None:
+                        tc = tout["counts"].cpu().numpy().view(np.uint32)
+                        need_rec, need_hello, need_sni = TLSDecoder.needed(tc)
+                        tls = dict(verdict=tout["verdict"].cpu().numpy(),
+                                   class_start=tout["class_start"].cpu().numpy().view(np.uint32), counts=tc,
+                                   index=tout["index"][:int(tc[0])].cpu().numpy().view(np.uint32),
+                                   records=tout["records"][:int(tc[0]) * _lib.TLS_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.TLS_DTYPE),
+                                   recs=tout["recs"][:need_rec * _lib.TLS_REC_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.TLS_REC_DTYPE),
+                                   hellos=tout["hellos"][:need_hello * _lib.TLS_HELLO_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.TLS_HELLO_DTYPE),
+                                   snis=tout["snis"][:need_sni].cpu().numpy())
                     if out is None:
                         self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns)
+                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls)
                         continue
                     m = int(out["counts"][0].item())
                     pl = dict(verdict=out["verdict"].cpu().numpy(),
@@ -1136,7 +1167,7 @@ class TunnelBatchResult:
                               tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
                                   _lib.TUNNEL_DTYPE))
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns)
+                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls)
                     for lt, js in self._next_work(part, level):
                         if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
                             io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
@@ -1146,7 +1177,7 @@ class TunnelBatchResult:
                         nxt.append((lt, index[pl["index"][js]], io, ic))
                 work, level = nxt, level + 1
         finally:
-            for h in (det, ctd, dnd):
+            for h in (det, ctd, dnd, tld):
                 if h is not None:
                     h.close()
 
@@ -1186,6 +1217,46 @@ class TunnelBatchResult:
         r0 = int(t["rr0"])
         return t, part.dns["rrs"][r0:r0 + int(t["nrr"])], part.dns["names"]
 
+    def _tls(self, part, pos):
+        """The gpk_tls record of a part's packet, or None: not a candidate."""
+        if part.tls is None:
+            return None
+        v = int(part.tls["verdict"][pos])
+        return part.tls["records"][v] if v >= 0 else None
+
+    @staticmethod
+    def _tls_entries(part, t):
+        r0, h0 = int(t["rec0"]), int(t["hello0"])
+        return part.tls["recs"][r0:r0 + int(t["nrec"])], part.tls["hellos"][h0:h0 + int(t["nhello"])]
+
+    def TLS(self, i):
+        """(the gpk_tls record (TLS_DTYPE), its gpk_tls_rec entries
+        (TLS_REC_DTYPE), its gpk_tls_hello entries (TLS_HELLO_DTYPE), the
+        server name arena) of packet i, or None: not a candidate. A failed
+        message has no entries."""
+        part, pos = self._chain[i][-1]
+        t = self._tls(part, pos)
+        if t is None:
+            return None
+        return (t,) + self._tls_entries(part, t) + (part.tls["snis"],)
+
+    def SNIs(self):
+        """[(packet index, server name bytes)] of every ClientHello of the
+        batch that carries a server name, in packet order: from the hello
+        entries and the name arena alone, no packet byte is touched."""
+        out = []
+        for lvl in self.levels:
+            for part in lvl:
+                if part.tls is None:
+                    continue
+                arena = part.tls["snis"]
+                for h in part.tls["hellos"]:
+                    if int(h["has_sni"]):
+                        at = int(h["sni_pos"])
+                        out.append((int(part.index[int(h["packet"])]), bytes(arena[at:at + int(h["sni_len"])])))
+        out.sort(key=lambda x: x[0])
+        return out
+
     def Control(self, i):
         """The gpk_control record (CONTROL_DTYPE) of packet i, or None."""
         return self._control(*self._chain[i][-1])
@@ -1203,6 +1274,9 @@ class TunnelBatchResult:
             d = self._dns(part, pos)
             if d is not None and not int(d["err"]):
                 out.append(LayerType(_lib.LT_DNS))
+            s = self._tls(part, pos)
+            if s is not None and not int(s["err"]):
+                out.append(LayerType(_lib.LT_TLS))
         return out
 
     def Truncated(self, i):
@@ -1211,9 +1285,11 @@ class TunnelBatchResult:
             t = self._tunnel(part, pos)
             c = self._control(part, pos)
             d = self._dns(part, pos)
+            s = self._tls(part, pos)
             tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED)) \
                 or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED)) \
-                or (d is not None and bool(int(d["status"]) & _lib.DNS_ST_TRUNCATED))
+                or (d is not None and bool(int(d["status"]) & _lib.DNS_ST_TRUNCATED)) \
+                or (s is not None and bool(int(s["status"]) & _lib.TLS_ST_TRUNCATED))
         return tr
 
     def Err(self, i):
@@ -1222,6 +1298,17 @@ class TunnelBatchResult:
         part, pos = self._chain[i][-1]
         t = self._tunnel(part, pos)
         c = self._control(part, pos)
+        s = self._tls(part, pos)
+        if s is not None:  # TLS has no payload: its error, or nil (tls.go:202-209)
+            code = int(s["err"])
+            if code:
+                buf = ctypes.create_string_buffer(256)
+                _lib.lib().gpk_tls_format_error(code, int(s["err_a0"]), int(s["err_a1"]), buf, 256)
+                msg = buf.value.decode()
+                if code == _lib.ERR_PANIC_SLICE_B and self.parser.IgnorePanic:
+                    raise GoPanic(msg[len("panic: "):])
+                return GoError(msg)
+            return None
         d = self._dns(part, pos)
         if d is not None:  # DNS has no payload: its error, or nil (dns.go:434-436)
             if int(d["err"]):
@@ -1280,6 +1367,9 @@ class TunnelBatchResult:
             if d is not None and not int(d["err"]):
                 r0 = int(d["rr0"])
                 p._dns._from_record(d, part.dns["rrs"][r0:r0 + int(d["nrr"])], part.dns["names"], part.batch.packet(pos))
+            s = self._tls(part, pos)
+            if s is not None and not int(s["err"]):
+                p._tls._from_record(s, *self._tls_entries(part, s), part.batch.packet(pos))
         decoded[:] = self.Decoded(i)
         p.Truncated = self.Truncated(i)
         return self.Err(i)

@@ -7,7 +7,9 @@ control layers ICMPv4, ICMPv6, ICMPv6Echo, ARP (layers/{icmp4,icmp6,icmp6msg,
 arp}.go), filled from the gpk_control record of gpk_control_batch
 (include/gpk_control.h), and DNS (layers/dns.go), filled from the gpk_dns
 record, the gpk_dns_rr entries and the name arena of gpk_dns_batch
-(include/gpk_dns.h).
+(include/gpk_dns.h), and TLS (layers/tls*.go), filled from the gpk_tls record
+and the gpk_tls_rec and gpk_tls_hello entries of gpk_tls_batch
+(include/gpk_tls.h).
 
 These structs are filled from device results, in one of two ways:
 - _fill(pkt, s, e, f): from the gpk_fields record the device wrote for the
@@ -1807,3 +1809,194 @@ class DNS(BaseLayer):
         sections = (self.Questions, self.Answers, self.Authorities, self.Additionals)
         for r in rrs:
             sections[int(r["section"])].append(_dns_entry(r, names, pkt))
+
+
+# ---- layers/tls.go, tls_handshake.go, tls_alert.go, tls_cipherspec.go, tls_appdata.go ------------
+# A DecodingLayerParser that holds layers.TLS decodes the messages on the device
+# after the DNS pass (gpk_tls_batch); the struct is filled from the packet's
+# gpk_tls record, its gpk_tls_rec and gpk_tls_hello entries and the packet's
+# bytes (_from_record). TLS.SerializeTo is not built.
+class TLSType(int):
+    """tls.go:17-42"""
+
+    def String(self):
+        return {20: "Change Cipher Spec", 21: "Alert", 22: "Handshake", 23: "Application Data"}.get(int(self), "Unknown")
+
+    __str__ = String
+
+
+class TLSVersion(int):
+    """tls.go:45-65"""
+
+    def String(self):
+        return {0x0200: "SSL 2.0", 0x0300: "SSL 3.0", 0x0301: "TLS 1.0", 0x0302: "TLS 1.1", 0x0303: "TLS 1.2",
+                0x0304: "TLS 1.3"}.get(int(self), "Unknown")
+
+    __str__ = String
+
+
+class TLSAlertLevel(int):
+    """tls_alert.go:17,98-107"""
+
+    def String(self):
+        return {1: "Warning", 2: "Fatal"}.get(int(self), "Unknown(%d)" % int(self))
+
+    __str__ = String
+
+
+_TLS_ALERT_DESCR = {
+    0: "close_notify", 10: "unexpected_message", 20: "bad_record_mac", 21: "decryption_failed_RESERVED",
+    22: "record_overflow", 30: "decompression_failure", 40: "handshake_failure", 41: "no_certificate_RESERVED",
+    42: "bad_certificate", 43: "unsupported_certificate", 44: "certificate_revoked", 45: "certificate_expired",
+    46: "certificate_unknown", 47: "illegal_parameter", 48: "unknown_ca", 49: "access_denied", 50: "decode_error",
+    51: "decrypt_error", 60: "export_restriction_RESERVED", 70: "protocol_version", 71: "insufficient_security",
+    80: "internal_error", 90: "user_canceled", 100: "no_renegotiation", 110: "unsupported_extension"}
+
+
+class TLSAlertDescr(int):
+    """tls_alert.go:20,110-165"""
+
+    def String(self):
+        return _TLS_ALERT_DESCR.get(int(self), "Unknown")
+
+    __str__ = String
+
+
+class TLSchangeCipherSpec(int):
+    """tls_cipherspec.go:16,57-64"""
+
+    def String(self):
+        return "Change Cipher Spec Message" if int(self) == 1 else "Unknown"
+
+    __str__ = String
+
+
+TLSChangeCipherSpec, TLSAlert, TLSHandshake, TLSApplicationData, TLSUnknown = (TLSType(x) for x in (20, 21, 22, 23, 255))
+TLSAlertWarning, TLSAlertFatal, TLSAlertUnknownLevel = (TLSAlertLevel(x) for x in (1, 2, 255))
+TLSAlertUnknownDescription = TLSAlertDescr(255)
+TLSChangecipherspecMessage, TLSChangecipherspecUnknown = TLSchangeCipherSpec(1), TLSchangeCipherSpec(255)
+(TLSHandshakeHelloRequest, TLSHandshakeClientHello, TLSHandshakeServerHello, TLSHandsharkHelloVerirfyRequest,
+ TLSHandshakeCertificate, TLSHandshakeServerKeyExchange, TLSHandshakeCertificateRequest, TLSHandshakeServerHelloDone,
+ TLSHandshakeCertificateVerify, TLSHandshakeClientKeyExchange, TLSHandshakeFinished) = (0, 1, 2, 3, 11, 12, 13, 14, 15,
+                                                                                        16, 20)
+
+
+@dataclass
+class TLSRecordHeader:
+    ContentType: TLSType = TLSType(0)
+    Version: TLSVersion = TLSVersion(0)
+    Length: int = 0
+
+
+@dataclass
+class TLSChangeCipherSpecRecord:
+    TLSRecordHeader: TLSRecordHeader = field(default_factory=TLSRecordHeader)
+    Message: TLSchangeCipherSpec = TLSchangeCipherSpec(0)
+
+
+@dataclass
+class TLSAppDataRecord:
+    TLSRecordHeader: TLSRecordHeader = field(default_factory=TLSRecordHeader)
+    Payload: Optional[bytes] = None
+
+
+@dataclass
+class TLSAlertRecord:
+    TLSRecordHeader: TLSRecordHeader = field(default_factory=TLSRecordHeader)
+    Level: TLSAlertLevel = TLSAlertLevel(0)
+    Description: TLSAlertDescr = TLSAlertDescr(0)
+    EncryptedMsg: Optional[bytes] = None
+
+
+@dataclass
+class TLSHandshakeRecordClientHello:
+    HandshakeType: int = 0
+    Length: int = 0
+    ProtocolVersion: TLSVersion = TLSVersion(0)
+    Random: Optional[bytes] = None
+    SessionIDLength: int = 0
+    SessionID: Optional[bytes] = None
+    CipherSuitsLength: int = 0
+    CipherSuits: Optional[bytes] = None
+    CompressionMethodsLength: int = 0
+    CompressionMethods: Optional[bytes] = None
+    ExtensionsLength: int = 0
+    Extensions: Optional[bytes] = None
+    SNI: Optional[bytes] = None
+
+
+@dataclass
+class TLSHandshakeRecordClientKeyChange:
+    pass
+
+
+@dataclass
+class TLSHandshakeRecord:
+    TLSRecordHeader: TLSRecordHeader = field(default_factory=TLSRecordHeader)
+    ClientHello: TLSHandshakeRecordClientHello = field(default_factory=TLSHandshakeRecordClientHello)
+    ClientKeyChange: TLSHandshakeRecordClientKeyChange = field(default_factory=TLSHandshakeRecordClientKeyChange)
+
+
+def _tls_hello(h, pkt):
+    """A TLSHandshakeRecordClientHello from a gpk_tls_hello entry and the packet's bytes."""
+    def cut(off, n):
+        o = int(h[off])
+        return bytes(pkt[o:o + n])
+    sid, cs = int(h["session_id_length"]), int(h["cipher_suits_length"])
+    cm, ext = int(h["compression_methods_length"]), int(h["extensions_length"])
+    return TLSHandshakeRecordClientHello(
+        int(h["handshake_type"]), int(h["length"]), TLSVersion(int(h["protocol_version"])), cut("random_off", 32), sid,
+        cut("session_id_off", sid), cs, cut("cipher_suits_off", cs), cm, cut("compression_methods_off", cm), ext,
+        cut("extensions_off", ext), cut("sni_off", int(h["sni_len"])) if int(h["has_sni"]) else None)
+
+
+class TLS(BaseLayer):
+    """tls.go:84-209. Payload() is nil: nothing follows a TLS layer."""
+    kind = 301
+    tls_kind = _lib.TLS_KIND
+
+    def __init__(self):
+        self._reset()
+
+    def _reset(self):
+        self.ChangeCipherSpec, self.Handshake, self.AppData, self.Alert = [], [], [], []
+        self.Contents = self.Payload = b""
+
+    def LayerType(self):
+        return LayerTypeTLS
+
+    def CanDecode(self):
+        return LayerClass([LayerTypeTLS])
+
+    def NextLayerType(self):
+        return LayerType(0)  # gopacket.LayerTypeZero
+
+    def LayerPayload(self):
+        return b""
+
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("TLS decodes through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+    def SerializeTo(self, b, opts):
+        raise NotImplementedError("TLS.SerializeTo is not built")
+
+    def _from_record(self, t, recs, hellos, pkt):
+        """t: the gpk_tls record (decoded, not dropped); recs, hellos: its entries."""
+        self._reset()
+        end = int(t["hdr_off"]) + int(t["len"])
+        for r in recs:
+            ct, o, n = int(r["content_type"]), int(r["body_off"]), int(r["length"])
+            hdr = TLSRecordHeader(TLSType(ct), TLSVersion(int(r["version"])), n)
+            if ct == 20:
+                self.ChangeCipherSpec.append(TLSChangeCipherSpecRecord(hdr, TLSchangeCipherSpec(int(r["v0"]))))
+            elif ct == 21:
+                self.Alert.append(TLSAlertRecord(hdr, TLSAlertLevel(int(r["v0"])), TLSAlertDescr(int(r["v1"])),
+                                                 None if n == 2 else bytes(pkt[o:o + n])))
+            elif ct == 22:
+                rec = TLSHandshakeRecord(hdr)
+                if int(r["hs"]) == _lib.TLS_HS_CLIENT_HELLO:
+                    rec.ClientHello = _tls_hello(hellos[int(r["hello"])], pkt)
+                self.Handshake.append(rec)
+            else:
+                self.AppData.append(TLSAppDataRecord(hdr, bytes(pkt[o:o + n])))
+            self.Contents = bytes(pkt[o - 5:end])  # tls.go:139: reset for every record, the last one's stays
