@@ -123,6 +123,8 @@ EXPORTS = (
     "gpk_dns_decoder_create", "gpk_dns_decoder_destroy", "gpk_dns_batch", "gpk_dns_batch_host", "gpk_dns_format_error",
     # include/gpk_tls.h
     "gpk_tls_decoder_create", "gpk_tls_decoder_destroy", "gpk_tls_batch", "gpk_tls_batch_host", "gpk_tls_format_error",
+    # include/gpk_tls_streams.h
+    "gpk_tls_stream_decoder_create", "gpk_tls_stream_decoder_destroy", "gpk_tls_streams", "gpk_tls_streams_host",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -381,6 +383,38 @@ class Tlss(ctypes.Structure):
                 ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("recs", ctypes.c_void_p),
                 ("hellos", ctypes.c_void_p), ("snis", ctypes.c_void_p), ("rec_cap", ctypes.c_uint64),
                 ("hello_cap", ctypes.c_uint64), ("sni_cap", ctypes.c_uint64)]
+
+
+# include/gpk_tls_streams.h constants
+TLSS_NEW, TLSS_SYNCED, TLSS_NONE, TLSS_NOSTART, TLSS_NOT_TLS, TLSS_LOST, TLSS_CLOSED = range(7)
+TLSS_NSTATE = 7
+TLSS_ST_DROPPED, TLSS_ST_TOOBIG, TLSS_ST_BADTAIL = 1, 2, 4
+TLSS_FRAME_UNSTARTED = 1
+TLSS_MAX_TAIL = 65539
+# gpk_tls_stream (64 B): one stream of a call
+TLS_STREAM_DTYPE = np.dtype([
+    ("state", "u1"), ("status", "u1"), ("reserved", "<u2"), ("tail_in", "<u4"), ("consumed", "<u4"),
+    ("tail_len", "<u4"), ("tail_off", "<u8"), ("nrec", "<u4"), ("nfailed", "<u4"), ("nhello", "<u4"),
+    ("sni_bytes", "<u4"), ("rec0", "<u8"), ("hello0", "<u8"), ("sni0", "<u8")])
+# gpk_tls_stream_rec (32 B): one record of a stream
+TLS_STREAM_REC_DTYPE = np.dtype([
+    ("rec", TLS_REC_DTYPE), ("err", "u1"), ("status", "u1"), ("reserved", "<u2"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("stream", "<u4")])
+
+
+class TlsStreamIn(ctypes.Structure):
+    """gpk_tls_stream_in: what the streams carry into a gpk_tls_streams call."""
+    _fields_ = [("state", ctypes.c_void_p), ("tail_off", ctypes.c_void_p), ("tail_len", ctypes.c_void_p),
+                ("tails", ctypes.c_void_p), ("n", ctypes.c_uint64), ("tail_bytes", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class TlsStreamOut(ctypes.Structure):
+    """gpk_tls_stream_out: the outputs of gpk_tls_streams."""
+    _fields_ = [("streams", ctypes.c_void_p), ("recs", ctypes.c_void_p), ("hellos", ctypes.c_void_p),
+                ("snis", ctypes.c_void_p), ("tails", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("rec_cap", ctypes.c_uint64), ("hello_cap", ctypes.c_uint64), ("sni_cap", ctypes.c_uint64),
+                ("tail_cap", ctypes.c_uint64)]
 
 
 # include/gpk_afpacket.h constants
@@ -682,6 +716,11 @@ def lib():
         "gpk_tls_batch": ([vp, vp, vp, P(Batch), P(Results), P(Tlss), vp], c_int),
         "gpk_tls_batch_host": ([vp, P(Batch), P(Results), P(Tlss)], c_int),
         "gpk_tls_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_tls_stream_decoder_create": ([P(vp), c_int, u64], c_int),
+        "gpk_tls_stream_decoder_destroy": ([vp], c_int),
+        "gpk_tls_streams": ([vp, vp, vp, P(Batch), P(Results), P(TcpStreams), P(TlsStreamIn), P(TlsStreamOut), vp],
+                            c_int),
+        "gpk_tls_streams_host": ([vp, P(Batch), P(Results), P(TcpStreams), P(TlsStreamIn), P(TlsStreamOut)], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

@@ -5,10 +5,16 @@
 //
 //   client_hello   TLSHandshakeRecordClientHello.decodeFromBytes over the body
 //                  re-sliced to the end of the packet, with the extension walk
-//   walk<kStore>   TLS.DecodeFromBytes: decodeTLSRecords as a loop, in two modes
-//                  of one function: size only (class, error, the counts and the
-//                  server name bytes), and store (the gpk_tls_rec and
-//                  gpk_tls_hello entries and the server names as well)
+//   record<kStore> one round of decodeTLSRecords: the header checks and the
+//                  per-type decode of one record, in two modes of one function:
+//                  size only (error, the counts and the server name bytes), and
+//                  store (the gpk_tls_rec and gpk_tls_hello entry and the server
+//                  name as well). The per-packet walk and the stream walk of
+//                  gpk_tls_streams.hip both call it.
+//   walk<kStore>   TLS.DecodeFromBytes: decodeTLSRecords as a loop over record
+//   Seam           the bytes of two buffers end to end, for the one record of a
+//                  stream that straddles the carried tail and the new bytes
+// The functions that read bytes take them as B: a const uint8_t*, or a Seam.
 //   tls            one packet: tun::candidate, then walk<false>
 // The lane's state is scalars only: no array is indexed at run time.
 #pragma once
@@ -21,6 +27,21 @@ namespace gpk {
 namespace tls {
 
 using tun::be16;
+
+// A logical buffer a[0..na) followed by b[0..): what a const uint8_t* offers the
+// rules (index, + offset), over the seam between a stream's tail and its new bytes.
+struct Seam {
+  const uint8_t* a;
+  const uint8_t* b;
+  uint32_t na, at;
+  GPK_HD uint8_t operator[](uint32_t i) const {
+    const uint32_t k = at + i;
+    return k < na ? a[k] : b[k - na];
+  }
+  GPK_HD Seam operator+(uint32_t k) const { return Seam{a, b, na, at + k}; }
+};
+
+GPK_HD uint32_t be16(const Seam& p) { return (uint32_t)p[0] << 8 | p[1]; }
 
 // A gpk_tls being decoded, one dword per field (as dns::Msg)
 struct Msg {
@@ -94,7 +115,8 @@ GPK_HD void hello_store(gpk_tls_hello* dst, const Hello& h, uint32_t pkt, uint64
 
 // decodeFromBytes(data[:cap(data)]) of a ClientHello: d is the record's body at
 // packet offset body_off, avail the bytes from there to the end of the packet.
-GPK_HD uint32_t client_hello(const uint8_t* d, uint32_t avail, uint32_t body_off, Hello& h) {
+template <typename B>
+GPK_HD uint32_t client_hello(const B& d, uint32_t avail, uint32_t body_off, Hello& h) {
   h.has_sni = h.sni_off = h.sni_len = h.a0 = h.a1 = 0;
   if (avail < 39) return GPK_TLS_ERR_HELLO_SHORT;
   h.type = d[0];
@@ -147,12 +169,83 @@ GPK_HD uint32_t client_hello(const uint8_t* d, uint32_t avail, uint32_t body_off
 }
 
 // isEncryptedHandshakeMessage; body holds length >= 16 bytes when it reads them
-GPK_HD bool encrypted_handshake(const uint8_t* body, uint32_t length) {
+template <typename B>
+GPK_HD bool encrypted_handshake(const B& body, uint32_t length) {
   if (length < 16) return false;
   const uint32_t be24 = (uint32_t)body[1] << 16 | be16(body + 2);
   if (length - be24 != 4u) return true;  // uint32 arithmetic
   const uint32_t t = body[0];
   return !(t <= 3 || (t >= 11 && t <= 16) || t == 20);
+}
+
+// One round of decodeTLSRecords (tls.go:130-194): d is at the record's header,
+// left the bytes from there to the end of the data, avail those to the end of
+// the buffer (>= left), body_off the offset reported for the body. Returns 0 and
+// the record's body length in `length`, or the error with its arguments in a0,
+// a1. m counts the record; kStore: it goes to *rec, its hello to
+// hellos[m.nhello] and its server name to snis + sni0 + m.sni_bytes (the caller
+// has checked that they fit); pkt is what the hello entry names.
+template <bool kStore, typename B>
+GPK_HD uint32_t record(const B& d, uint32_t left, uint32_t avail, uint32_t body_off, Msg& m, uint32_t pkt,
+                       gpk_tls_rec* rec, gpk_tls_hello* hellos, uint8_t* snis, uint64_t sni0, uint32_t& length,
+                       uint32_t& a0, uint32_t& a1) {
+  a0 = a1 = 0;
+  if (left < 5) return GPK_TLS_ERR_RECORD_SHORT;
+  const uint32_t ct = d[0], version = be16(d + 1);
+  length = be16(d + 3);
+  if (ct < 20 || ct > 23) return GPK_TLS_ERR_RECORD_TYPE;
+  if (left < 5 + length) return GPK_TLS_ERR_LENGTH_MISMATCH;
+  const B body = d + 5;
+  uint32_t hs = GPK_TLS_HS_NONE, v0 = 0, v1 = 0, hello = GPK_TLS_NO_HELLO;
+  if (ct == 20) {
+    if (length != 1) return GPK_TLS_ERR_CCS_LENGTH;
+    v0 = body[0] == 1 ? 1u : 255u;
+    m.nccs++;
+  } else if (ct == 21) {
+    if (length < 2) return GPK_TLS_ERR_ALERT_SHORT;
+    v0 = length == 2 ? body[0] : 255u;
+    v1 = length == 2 ? body[1] : 255u;
+    m.nalert++;
+  } else if (ct == 22) {
+    if (encrypted_handshake(body, length)) {
+      hs = GPK_TLS_HS_ENCRYPTED;
+    } else {
+      if (length < 1) return GPK_TLS_ERR_HANDSHAKE_SHORT;
+      const uint32_t t = body[0];
+      if (t == 1) {
+        Hello h;
+        if (const uint32_t e = client_hello(body, avail - 5, body_off, h)) {
+          a0 = h.a0, a1 = h.a1;
+          return e;
+        }
+        hs = GPK_TLS_HS_CLIENT_HELLO;
+        hello = m.nhello;
+        if (kStore) {
+          const uint64_t at = sni0 + m.sni_bytes;
+          hello_store(hellos + m.nhello, h, pkt, at);
+          const B src = body + (h.sni_off - body_off);
+          for (uint32_t i = 0; i < h.sni_len; i++) snis[at + i] = src[i];
+        }
+        m.nhello++;
+        m.sni_bytes += h.sni_len;
+      } else if (t == 16) {
+        hs = GPK_TLS_HS_CLIENT_KEY;
+      } else {
+        return GPK_TLS_ERR_HANDSHAKE_TYPE;
+      }
+    }
+    m.nhs++;
+  } else {
+    m.napp++;
+  }
+  if (kStore) {
+    uint32_t* w = reinterpret_cast<uint32_t*>(rec);
+    w[0] = ct | hs << 8 | v0 << 16 | v1 << 24;
+    w[1] = version | length << 16;
+    w[2] = body_off;
+    w[3] = hello;
+  }
+  return 0;
 }
 
 // TLS.DecodeFromBytes(d[:len]); avail: the bytes from d to the end of the
@@ -165,59 +258,10 @@ GPK_HD void walk(const uint8_t* d, uint32_t len, uint32_t avail, Msg& m, uint32_
   m.len = len;
   uint32_t k = 0;
   for (uint32_t off = 0;;) {
-    const uint32_t left = len - off;
-    if (left < 5) return fail(m, GPK_TLS_ERR_RECORD_SHORT, 0, 0);
-    const uint32_t ct = d[off], version = be16(d + off + 1), length = be16(d + off + 3);
-    if (ct < 20 || ct > 23) return fail(m, GPK_TLS_ERR_RECORD_TYPE, 0, 0);
-    if (left < 5 + length) return fail(m, GPK_TLS_ERR_LENGTH_MISMATCH, 0, 0);
-    const uint8_t* body = d + off + 5;
-    const uint32_t body_off = m.hdr_off + off + 5;
-    uint32_t hs = GPK_TLS_HS_NONE, v0 = 0, v1 = 0, hello = GPK_TLS_NO_HELLO;
-    if (ct == 20) {
-      if (length != 1) return fail(m, GPK_TLS_ERR_CCS_LENGTH, 0, 0);
-      v0 = body[0] == 1 ? 1u : 255u;
-      m.nccs++;
-    } else if (ct == 21) {
-      if (length < 2) return fail(m, GPK_TLS_ERR_ALERT_SHORT, 0, 0);
-      v0 = length == 2 ? body[0] : 255u;
-      v1 = length == 2 ? body[1] : 255u;
-      m.nalert++;
-    } else if (ct == 22) {
-      if (encrypted_handshake(body, length)) {
-        hs = GPK_TLS_HS_ENCRYPTED;
-      } else {
-        if (length < 1) return fail(m, GPK_TLS_ERR_HANDSHAKE_SHORT, 0, 0);
-        const uint32_t t = body[0];
-        if (t == 1) {
-          Hello h;
-          if (const uint32_t e = client_hello(body, avail - off - 5, body_off, h)) return fail(m, e, h.a0, h.a1);
-          hs = GPK_TLS_HS_CLIENT_HELLO;
-          hello = m.nhello;
-          if (kStore) {
-            const uint64_t at = sni0 + m.sni_bytes;
-            hello_store(hellos + m.nhello, h, pkt, at);
-            const uint8_t* src = d + (h.sni_off - m.hdr_off);
-            for (uint32_t i = 0; i < h.sni_len; i++) snis[at + i] = src[i];
-          }
-          m.nhello++;
-          m.sni_bytes += h.sni_len;
-        } else if (t == 16) {
-          hs = GPK_TLS_HS_CLIENT_KEY;
-        } else {
-          return fail(m, GPK_TLS_ERR_HANDSHAKE_TYPE, 0, 0);
-        }
-      }
-      m.nhs++;
-    } else {
-      m.napp++;
-    }
-    if (kStore) {
-      uint32_t* w = reinterpret_cast<uint32_t*>(recs + k);
-      w[0] = ct | hs << 8 | v0 << 16 | v1 << 24;
-      w[1] = version | length << 16;
-      w[2] = body_off;
-      w[3] = hello;
-    }
+    uint32_t length, a0, a1;
+    if (const uint32_t e = record<kStore>(d + off, len - off, avail - off, m.hdr_off + off + 5, m, pkt,
+                                          kStore ? recs + k : nullptr, hellos, snis, sni0, length, a0, a1))
+      return fail(m, e, a0, a1);
     k++;
     off += 5 + length;
     if (off == len) return;

@@ -51,6 +51,11 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            of the packets whose decode stopped in front of
                                            LayerTypeTLS: message records, one entry per TLS
                                            record and per ClientHello, and the server names
+  TLSStreamDecoder(max_streams).decode(...) gpk_tls_streams (include/gpk_tls_streams.h): the TLS
+                                           records of the streams Assembler.assemble laid out:
+                                           record boundaries, the unfinished tail, one entry per
+                                           record and per ClientHello, and the server names
+  TLSStreams(ctx, parser, n)               the same over a stream of batches, on a TCPAssembler
 """
 import ctypes
 
@@ -638,6 +643,7 @@ class TCPAssembler:
         self._carry = None  # (data, offsets, caplens, code[], seq[], gid[], origin[(batch, index)])
         self._streams = 0   # global ids handed out so far
         self._batch = 0
+        self._last = None   # the device arrays of the last call that had packets
 
     @property
     def open_count(self):
@@ -704,6 +710,7 @@ class TCPAssembler:
         bno = self._batch
         if count_batch:
             self._batch += 1
+        self._last = None
         if n == 0:
             return dict(verdict=[], stream_of=[], streams=[], data=torch.empty(0, dtype=torch.uint8, device=dev),
                         counts=[0] * 8, **(dict(flushed=0, closed=0) if self.timed else {}))
@@ -758,6 +765,9 @@ class TCPAssembler:
                     t = at + tcp
                     streams[j]["key"] = (6 if six else 4, hd[a:a + w].tobytes(), hd[a + w:a + 2 * w].tobytes(),
                                          hd[t:t + 2].tobytes(), hd[t + 2:t + 4].tobytes())
+        # for a pass over the streams of this call (TLSStreams): the device arrays as the assembler saw them
+        self._last = dict(data=data, offsets=offsets, caplens=caplens, records=rec, layouts=lay, out=out, ids=ids,
+                          stream=st)
         so = out["stream_of"][P:].cpu().tolist()
         result = dict(verdict=out["verdict"][P:].cpu().tolist(), stream_of=[ids[x] if x >= 0 else -1 for x in so],
                       streams=streams, data=out["data"], counts=counts)
@@ -1189,3 +1199,236 @@ class TLSDecoder(_PostPass):
         if int(out["counts"][3]):
             out = cls.decode_host(data, offsets, caplens, records, layouts, parser, *cls.needed(out["counts"]))
         return out
+
+
+class TLSStreamDecoder(_Handle):
+    """gpk_tls_streams (include/gpk_tls_streams.h): the TLS records of the
+    streams of one Assembler.assemble call. Owns the workspace of the scans for
+    calls of up to max_streams packets; device=None makes a host-only one
+    (decode_host).
+
+    The result is variable-length: streams[S] (TLS_STREAM_DTYPE) name ranges
+    of recs[rec_cap] (TLS_STREAM_REC_DTYPE, one per TLS record), of
+    hellos[hello_cap] (TLS_HELLO_DTYPE; packet holds the stream's index), of
+    the byte arena snis[sni_cap] and of the tail arena tails[tail_cap]. A
+    stream whose range does not fit every capacity is not written
+    (TLSS_ST_DROPPED); counts tells what the call needs (needed()), and
+    decode_all / decode_host_all size first and decode once more with exactly
+    that. `carry` is (state, tail_off, tail_len, tails) of the call's first
+    len(state) streams: uint32 / int32 states, int64 offsets and int32 lengths
+    into the uint8 arena `tails` (the `tails` output of the call before, which
+    must not be this call's output arena)."""
+
+    _create, _destroy = "gpk_tls_stream_decoder_create", "gpk_tls_stream_decoder_destroy"
+    KEYS = ("streams", "recs", "hellos", "snis", "tails", "counts")
+    ASM_KEYS = ("verdict", "stream_of", "chunks", "stream_group", "stream_first", "stream_closed", "stream_chunk0",
+                "stream_data0", "conn_seq", "conn_stream", "pend_pkt", "pend_page", "counts", "data")
+
+    def __init__(self, max_streams=1, device=0):
+        if device is None:  # host-only: no handle
+            self.h, self.max_packets = ctypes.c_void_p(), int(max_streams)
+        else:
+            super().__init__(max_streams, int(device))
+
+    @staticmethod
+    def needed(counts):
+        """(record entries, hello entries, server name bytes, tail bytes) the call needs, from counts[12]."""
+        return tuple(int(x) for x in counts[6:10])
+
+    @staticmethod
+    def _structs(ptr, numel, asm, carry, caps, out, frame_unstarted):
+        a = _lib.TcpStreams(*[ptr(asm[k]) if asm.get(k) is not None else None for k in TLSStreamDecoder.ASM_KEYS],
+                            int(asm.get("chunk_cap", numel(asm["chunks"]) // _lib.TCP_CHUNK_DTYPE.itemsize)),
+                            int(asm.get("data_cap", numel(asm["data"]))))
+        flags = _lib.TLSS_FRAME_UNSTARTED if frame_unstarted else 0
+        if carry is None:
+            i = _lib.TlsStreamIn(None, None, None, None, 0, 0, flags, 0)
+        else:
+            state, off, ln, tails = carry
+            nt = 0 if tails is None else numel(tails)
+            i = _lib.TlsStreamIn(ptr(state), ptr(off), ptr(ln), ptr(tails) if nt else None, numel(state), nt, flags, 0)
+        o = _lib.TlsStreamOut(ptr(out["streams"]), *[ptr(out[k]) if c else None for k, c in
+                                                     zip(("recs", "hellos", "snis", "tails"), caps)],
+                              ptr(out["counts"]), *caps)
+        return a, i, o
+
+    def decode(self, ctx, parser, data, offsets, caplens, records, layouts, asm, rec_cap, hello_cap, sni_cap, tail_cap,
+               carry=None, frame_unstarted=False, out=None, stream=None):
+        """Device tensors in: the batch the assembler was given, its records
+        and layouts, and `asm`, the dict Assembler.assemble returned for it.
+        Returns dict(streams[64 n] (uint8, _lib.TLS_STREAM_DTYPE), recs[32
+        rec_cap] (uint8, _lib.TLS_STREAM_REC_DTYPE), hellos[64 hello_cap],
+        snis[sni_cap], tails[tail_cap], counts[12] (int64)) of device tensors
+        (or fills `out`); stream entries at and past counts[0] are not written,
+        nor is anything past a capacity. Asynchronous on `stream`."""
+        import torch
+        caps = (int(rec_cap), int(hello_cap), int(sni_cap), int(tail_cap))
+        n, dev = offsets.numel(), offsets.device
+        if out is None:
+            u8 = torch.uint8
+            out = dict(streams=torch.empty(max(n, 1) * 64, dtype=u8, device=dev),
+                       recs=torch.empty(caps[0] * 32, dtype=u8, device=dev),
+                       hellos=torch.empty(caps[1] * 64, dtype=u8, device=dev),
+                       snis=torch.empty(caps[2], dtype=u8, device=dev), tails=torch.empty(caps[3], dtype=u8, device=dev),
+                       counts=torch.zeros(12, dtype=torch.int64, device=dev))
+        a, i, o = self._structs(lambda t: t.data_ptr(), lambda t: t.numel(), asm, carry, caps, out, frame_unstarted)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        _lib.check(_lib.lib().gpk_tls_streams(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                                              ctypes.byref(i), ctypes.byref(o), _lib.stream_ptr(stream)))
+        return out
+
+    def decode_all(self, ctx, parser, data, offsets, caplens, records, layouts, asm, rec_cap=0, hello_cap=0, sni_cap=0,
+                   tail_cap=0, carry=None, frame_unstarted=False, stream=None):
+        """decode with capacities that hold every stream: a first call with the
+        capacities given, and, when counts reports an overflow, a second one
+        with exactly the sizes it needs. With the default capacities of 0 the
+        first call only sizes. Synchronizes on the counts."""
+        out = self.decode(ctx, parser, data, offsets, caplens, records, layouts, asm, rec_cap, hello_cap, sni_cap,
+                          tail_cap, carry, frame_unstarted, stream=stream)
+        counts = out["counts"].cpu().tolist()
+        if counts[5]:
+            out = self.decode(ctx, parser, data, offsets, caplens, records, layouts, asm, *self.needed(counts),
+                              carry=carry, frame_unstarted=frame_unstarted, stream=stream)
+        return out
+
+    @classmethod
+    def decode_host(cls, parser, data, offsets, caplens, records, layouts, asm, rec_cap, hello_cap, sni_cap, tail_cap,
+                    carry=None, frame_unstarted=False, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_tls_streams_host); asm holds the assembler's outputs as numpy
+        arrays (chunks as _lib.TCP_CHUNK_DTYPE, stream_first, stream_closed,
+        stream_data0, counts, data at least); `fill` is the byte the outputs
+        start with."""
+        import numpy as np
+        caps = (int(rec_cap), int(hello_cap), int(sni_cap), int(tail_cap))
+        keep = (np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(offsets, np.uint64),
+                np.ascontiguousarray(caplens, np.uint32), np.ascontiguousarray(records, _lib.RECORD_DTYPE),
+                np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE))
+        n = len(keep[2])
+        asm = dict(asm)
+        for k, dt in (("chunks", _lib.TCP_CHUNK_DTYPE), ("stream_first", np.uint32), ("stream_closed", np.uint32),
+                      ("stream_data0", np.uint64), ("counts", np.uint64), ("data", np.uint8)):
+            asm[k] = np.ascontiguousarray(asm[k], dt)
+        asm.setdefault("chunk_cap", len(asm["chunks"]))
+        asm.setdefault("data_cap", len(asm["data"]))
+        if carry is not None:
+            carry = (np.ascontiguousarray(carry[0], np.uint32), np.ascontiguousarray(carry[1], np.uint64),
+                     np.ascontiguousarray(carry[2], np.uint32),
+                     None if carry[3] is None else np.ascontiguousarray(carry[3], np.uint8))
+        out = dict(streams=np.empty(max(n, 1), _lib.TLS_STREAM_DTYPE), recs=np.empty(caps[0], _lib.TLS_STREAM_REC_DTYPE),
+                   hellos=np.empty(caps[1], _lib.TLS_HELLO_DTYPE), snis=np.empty(caps[2], np.uint8),
+                   tails=np.empty(caps[3], np.uint8), counts=np.empty(12, np.uint64))
+        for v in out.values():
+            v.view(np.uint8)[:] = fill
+        a, i, o = cls._structs(lambda t: t.ctypes.data, lambda t: t.size, asm, carry, caps, out, frame_unstarted)
+        b = _lib.Batch(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, n, keep[0].size)
+        r = _lib.Results(keep[3].ctypes.data, None, None, keep[4].ctypes.data)
+        _lib.check(_lib.lib().gpk_tls_streams_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                                                   ctypes.byref(i), ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def decode_host_all(cls, parser, data, offsets, caplens, records, layouts, asm, rec_cap=0, hello_cap=0, sni_cap=0,
+                        tail_cap=0, carry=None, frame_unstarted=False):
+        """decode_host with the retry of decode_all."""
+        out = cls.decode_host(parser, data, offsets, caplens, records, layouts, asm, rec_cap, hello_cap, sni_cap,
+                              tail_cap, carry, frame_unstarted)
+        if int(out["counts"][5]):
+            out = cls.decode_host(parser, data, offsets, caplens, records, layouts, asm, *cls.needed(out["counts"]),
+                                  carry=carry, frame_unstarted=frame_unstarted)
+        return out
+
+
+class TLSStreamResult:
+    """What TLSStreams returns for one call. streams: [dict(id (global),
+    state (TLSS_*), status, tail_in, recs (TLS_STREAM_REC_DTYPE), hellos
+    (TLS_HELLO_DTYPE), names ([bytes or None] per hello), closed, and key with
+    keys=True on a new stream)]; offsets of recs and hellos are relative to
+    the stream's logical buffer of this call (tail_in carried bytes, then the
+    new ones). counts: gpk_tls_stream_out.counts. Only these tables and the
+    names come to the host, no stream byte."""
+
+    def __init__(self, streams, counts, assembled):
+        self.streams, self.counts, self.assembled = streams, counts, assembled
+
+    def snis(self):
+        """[(global stream id, server name)] in stream order."""
+        return [(s["id"], nm) for s in self.streams for nm in s["names"] if nm is not None]
+
+
+class TLSStreams:
+    """TLS over reassembled streams: a TCPAssembler and a TLSStreamDecoder
+    behind it, over a stream of device batches. The state and the unfinished
+    tail of every open stream are kept per global stream id; the tails stay on
+    the device. Every open connection is a stream of every call (it goes in as
+    a carried entry), so the tail arena of one call is the input arena of the
+    next. A closed stream's state is dropped."""
+
+    def __init__(self, ctx, parser, max_packets, max_pages=0, timed=False, frame_unstarted=False, device=0, keys=False):
+        self.ctx, self.parser = ctx, parser
+        self.asm = TCPAssembler(ctx, parser, max_packets, max_pages=max_pages, device=device, keys=keys, timed=timed)
+        self.decoder = TLSStreamDecoder(self.asm.max_packets, device)
+        self.frame_unstarted = bool(frame_unstarted)
+        self.device = device
+        self._state = {}    # global id -> (state, tail_off, tail_len) into _tails
+        self._tails = None
+
+    def feed(self, data, offsets, caplens, timestamps=None):
+        """One batch (as TCPAssembler.assemble). Returns a TLSStreamResult."""
+        return self._decode(self.asm.assemble(data, offsets, caplens, timestamps))
+
+    def flush_all(self):
+        return self._decode(self.asm.flush_all())
+
+    def flush_older_than(self, t):
+        return self._decode(self.asm.flush_older_than(t))
+
+    def _decode(self, res):
+        import numpy as np
+        import torch
+        last = self.asm._last
+        if last is None or not res["streams"]:
+            return TLSStreamResult([], [0] * 12, res)
+        ids = last["ids"]
+        S = len(ids)
+        n = last["offsets"].numel()
+        if n > self.decoder.max_packets:  # the assembler grew its workspaces
+            self.decoder.close()
+            self.decoder = TLSStreamDecoder(self.asm.max_packets, self.device)
+        dev = last["offsets"].device
+        st = np.zeros((3, S), np.int64)
+        for j, g in enumerate(ids):
+            st[:, j] = self._state.get(g, (_lib.TLSS_NEW, 0, 0))
+        carry = (torch.tensor(st[0], dtype=torch.int32, device=dev), torch.tensor(st[1], dtype=torch.int64, device=dev),
+                 torch.tensor(st[2], dtype=torch.int32, device=dev), self._tails)
+        out = self.decoder.decode_all(self.ctx, self.parser, last["data"], last["offsets"], last["caplens"],
+                                      last["records"], last["layouts"], last["out"], carry=carry,
+                                      frame_unstarted=self.frame_unstarted, stream=last["stream"])
+        self._last_call = dict(carry=carry, out=out)  # what went in beside asm._last, and what came out
+        counts = out["counts"].cpu().tolist()
+        ent = out["streams"].cpu().numpy().view(_lib.TLS_STREAM_DTYPE)[:S]
+        recs = out["recs"].cpu().numpy().view(_lib.TLS_STREAM_REC_DTYPE)
+        hellos = out["hellos"].cpu().numpy().view(_lib.TLS_HELLO_DTYPE)
+        snis = out["snis"].cpu().numpy()
+        self._tails = out["tails"]
+        streams = []
+        for j, (g, e, a) in enumerate(zip(ids, ent, res["streams"])):
+            r0, h0 = int(e["rec0"]), int(e["hello0"])
+            hs = hellos[h0:h0 + int(e["nhello"])]
+            names = [bytes(snis[int(h["sni_pos"]):int(h["sni_pos"]) + int(h["sni_len"])]) if int(h["has_sni"]) else None
+                     for h in hs]
+            d = dict(id=g, state=int(e["state"]), status=int(e["status"]), tail_in=int(e["tail_in"]),
+                     recs=recs[r0:r0 + int(e["nrec"])], hellos=hs, names=names, closed=a["closed"])
+            if "key" in a:
+                d["key"] = a["key"]
+            streams.append(d)
+            if a["closed"] is not None:
+                self._state.pop(g, None)
+            else:
+                self._state[g] = (int(e["state"]), int(e["tail_off"]), int(e["tail_len"]))
+        return TLSStreamResult(streams, counts, res)
+
+    def close(self):
+        self.asm.close()
+        self.decoder.close()

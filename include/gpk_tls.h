@@ -94,9 +94,10 @@
  *               reported.
  *   Streams     Each packet is decoded on its own, as the reference does: a
  *               ClientHello split over two TCP segments fails with "TLS
- *               packet length mismatch". TLS over reassembled streams,
- *               ServerHello and certificate decoding (the reference has
- *               none), DTLS, QUIC and TLS.SerializeTo are not built.
+ *               packet length mismatch". TLS over reassembled streams is
+ *               gpk_tls_streams (gpk_tls_streams.h). ServerHello and
+ *               certificate decoding (the reference has none), DTLS, QUIC
+ *               and TLS.SerializeTo are not built.
  */
 #ifndef GPK_TLS_H
 #define GPK_TLS_H
