@@ -125,6 +125,8 @@ EXPORTS = (
     "gpk_tls_decoder_create", "gpk_tls_decoder_destroy", "gpk_tls_batch", "gpk_tls_batch_host", "gpk_tls_format_error",
     # include/gpk_tls_streams.h
     "gpk_tls_stream_decoder_create", "gpk_tls_stream_decoder_destroy", "gpk_tls_streams", "gpk_tls_streams_host",
+    # include/gpk_dns_streams.h
+    "gpk_dns_stream_decoder_create", "gpk_dns_stream_decoder_destroy", "gpk_dns_streams", "gpk_dns_streams_host",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -414,6 +416,39 @@ class TlsStreamOut(ctypes.Structure):
     _fields_ = [("streams", ctypes.c_void_p), ("recs", ctypes.c_void_p), ("hellos", ctypes.c_void_p),
                 ("snis", ctypes.c_void_p), ("tails", ctypes.c_void_p), ("counts", ctypes.c_void_p),
                 ("rec_cap", ctypes.c_uint64), ("hello_cap", ctypes.c_uint64), ("sni_cap", ctypes.c_uint64),
+                ("tail_cap", ctypes.c_uint64)]
+
+
+# include/gpk_dns_streams.h constants
+DNSS_NEW, DNSS_SYNCED, DNSS_NONE, DNSS_NOSTART, DNSS_LOST, DNSS_CLOSED = range(6)
+DNSS_NSTATE = 6
+DNSS_ST_DROPPED, DNSS_ST_TOOBIG, DNSS_ST_BADTAIL = 1, 2, 4
+DNSS_MSG_PARTIAL, DNSS_MSG_SKIPPED, DNSS_MSG_DROPPED = 1, 2, 4
+DNSS_FRAME_UNSTARTED = 1
+DNSS_MAX_TAIL = 65536
+# gpk_dns_stream (64 B): one stream of a call
+DNS_STREAM_DTYPE = np.dtype([
+    ("state", "u1"), ("status", "u1"), ("reserved", "<u2"), ("tail_in", "<u4"), ("consumed", "<u4"),
+    ("tail_len", "<u4"), ("tail_off", "<u8"), ("nmsg", "<u4"), ("nfailed", "<u4"), ("msg0", "<u8"),
+    ("reserved2", "<u8", (3,))])
+# gpk_dns_stream_msg (80 B): one message of a stream
+DNS_STREAM_MSG_DTYPE = np.dtype([
+    ("msg", DNS_DTYPE), ("stream", "<u4"), ("status", "u1"), ("reserved", "u1", (3,)), ("present", "<u4"),
+    ("reserved2", "<u4")])
+
+
+class DnsStreamIn(ctypes.Structure):
+    """gpk_dns_stream_in: what the streams carry into a gpk_dns_streams call."""
+    _fields_ = [("state", ctypes.c_void_p), ("tail_off", ctypes.c_void_p), ("tail_len", ctypes.c_void_p),
+                ("tails", ctypes.c_void_p), ("n", ctypes.c_uint64), ("tail_bytes", ctypes.c_uint64),
+                ("flags", ctypes.c_uint32), ("max_msg_len", ctypes.c_uint32)]
+
+
+class DnsStreamOut(ctypes.Structure):
+    """gpk_dns_stream_out: the outputs of gpk_dns_streams."""
+    _fields_ = [("streams", ctypes.c_void_p), ("msgs", ctypes.c_void_p), ("rrs", ctypes.c_void_p),
+                ("names", ctypes.c_void_p), ("tails", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+                ("msg_cap", ctypes.c_uint64), ("rr_cap", ctypes.c_uint64), ("name_cap", ctypes.c_uint64),
                 ("tail_cap", ctypes.c_uint64)]
 
 
@@ -721,6 +756,11 @@ def lib():
         "gpk_tls_streams": ([vp, vp, vp, P(Batch), P(Results), P(TcpStreams), P(TlsStreamIn), P(TlsStreamOut), vp],
                             c_int),
         "gpk_tls_streams_host": ([vp, P(Batch), P(Results), P(TcpStreams), P(TlsStreamIn), P(TlsStreamOut)], c_int),
+        "gpk_dns_stream_decoder_create": ([P(vp), c_int, u64, u64], c_int),
+        "gpk_dns_stream_decoder_destroy": ([vp], c_int),
+        "gpk_dns_streams": ([vp, vp, vp, P(Batch), P(Results), P(TcpStreams), P(DnsStreamIn), P(DnsStreamOut), vp],
+                            c_int),
+        "gpk_dns_streams_host": ([vp, P(Batch), P(Results), P(TcpStreams), P(DnsStreamIn), P(DnsStreamOut)], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

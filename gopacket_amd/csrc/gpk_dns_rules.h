@@ -10,11 +10,15 @@
 //                  header fields), and emit (the gpk_dns_rr entries and the
 //                  name bytes as well)
 //   dns            one packet: tun::candidate, then walk<false>
+// The functions that read bytes take them as B: a const uint8_t*, or a Seam
+// (gpk_seam.h) for the one message of a stream that straddles the carried tail
+// and the new bytes (gpk_dns_streams.hip).
 // The lane's state is scalars only: no array is indexed at run time.
 #pragma once
 #include <stdint.h>
 
 #include "../../include/gpk_dns.h"
+#include "gpk_seam.h"
 #include "gpk_tunnel_rules.h"
 
 namespace gpk {
@@ -63,8 +67,8 @@ struct Cur {
 
 // decodeName(data[:len], offset, buffer, 1). The name's bytes go to c.names +
 // c.pos when kEmit; n: its length; end: the returned offset (the top level's).
-template <bool kEmit>
-GPK_HD uint32_t decode_name(const uint8_t* d, uint32_t len, uint32_t offset, Cur& c, uint32_t& n, uint32_t& end) {
+template <bool kEmit, typename B>
+GPK_HD uint32_t decode_name(const B& d, uint32_t len, uint32_t offset, Cur& c, uint32_t& n, uint32_t& end) {
   uint8_t* out = kEmit ? c.names + c.pos : nullptr;
   uint32_t off = offset;
   n = 0;
@@ -142,8 +146,8 @@ GPK_HD void rr_store(gpk_dns_rr* dst, const Rr& r) {
 }
 
 // the one RDATA name of most typed forms: into rname, the cursor moves on
-template <bool kEmit>
-GPK_HD uint32_t rdata_name(const uint8_t* d, uint32_t end, uint32_t off, Cur& c, Rr& r, uint32_t& endq) {
+template <bool kEmit, typename B>
+GPK_HD uint32_t rdata_name(const B& d, uint32_t end, uint32_t off, Cur& c, Rr& r, uint32_t& endq) {
   uint32_t n;
   if (const uint32_t e = decode_name<kEmit>(d, end, off, c, n, endq)) return e;
   r.rname_off = c.pos;
@@ -153,7 +157,8 @@ GPK_HD uint32_t rdata_name(const uint8_t* d, uint32_t end, uint32_t off, Cur& c,
 }
 
 // NAPTR's three character-strings (:1457-1489): missing, then truncated
-GPK_HD uint32_t naptr_string(const uint8_t* d, uint32_t end, uint32_t& off, uint32_t hdr_off, uint32_t& v_off,
+template <typename B>
+GPK_HD uint32_t naptr_string(const B& d, uint32_t end, uint32_t& off, uint32_t hdr_off, uint32_t& v_off,
                              uint32_t& v_len, uint32_t missing, uint32_t truncated) {
   if (end < off + 1) return missing;
   const uint32_t l = d[off];
@@ -166,8 +171,8 @@ GPK_HD uint32_t naptr_string(const uint8_t* d, uint32_t end, uint32_t& off, uint
 }
 
 // decodeRData(data[:end], off, buffer); r.type, r.data_length (> 0) and r.data_off are set
-template <bool kEmit>
-GPK_HD uint32_t rdata(const uint8_t* d, uint32_t end, uint32_t off, uint32_t hdr_off, Cur& c, Rr& r) {
+template <bool kEmit, typename B>
+GPK_HD uint32_t rdata(const B& d, uint32_t end, uint32_t off, uint32_t hdr_off, Cur& c, Rr& r) {
   uint32_t endq;
   switch (r.type) {
     case 16:
@@ -289,8 +294,8 @@ GPK_HD void fail(Msg& m, uint32_t code, uint32_t a0, uint32_t a1) {
 
 // DNS.DecodeFromBytes(d[:len]). kEmit: entry k of the message goes to rrs[k],
 // its names to names + name0 on (the caller has checked that both fit).
-template <bool kEmit>
-GPK_HD void walk(const uint8_t* d, uint32_t len, Msg& m, gpk_dns_rr* rrs, uint8_t* names, uint64_t name0) {
+template <bool kEmit, typename B>
+GPK_HD void walk(const B& d, uint32_t len, Msg& m, gpk_dns_rr* rrs, uint8_t* names, uint64_t name0) {
   if (len < 12) return fail(m, GPK_DNS_ERR_SHORT, 0, 0);
   m.len = len;
   m.id = be16(d);

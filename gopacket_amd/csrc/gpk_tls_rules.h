@@ -12,8 +12,8 @@
 //                  name as well). The per-packet walk and the stream walk of
 //                  gpk_tls_streams.hip both call it.
 //   walk<kStore>   TLS.DecodeFromBytes: decodeTLSRecords as a loop over record
-//   Seam           the bytes of two buffers end to end, for the one record of a
-//                  stream that straddles the carried tail and the new bytes
+//   Seam           (gpk_seam.h) the bytes of two buffers end to end, for the one record of
+//                  a stream that straddles the carried tail and the new bytes
 // The functions that read bytes take them as B: a const uint8_t*, or a Seam.
 //   tls            one packet: tun::candidate, then walk<false>
 // The lane's state is scalars only: no array is indexed at run time.
@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "../../include/gpk_tls.h"
+#include "gpk_seam.h"
 #include "gpk_tunnel_rules.h"
 
 namespace gpk {
@@ -28,20 +29,7 @@ namespace tls {
 
 using tun::be16;
 
-// A logical buffer a[0..na) followed by b[0..): what a const uint8_t* offers the
-// rules (index, + offset), over the seam between a stream's tail and its new bytes.
-struct Seam {
-  const uint8_t* a;
-  const uint8_t* b;
-  uint32_t na, at;
-  GPK_HD uint8_t operator[](uint32_t i) const {
-    const uint32_t k = at + i;
-    return k < na ? a[k] : b[k - na];
-  }
-  GPK_HD Seam operator+(uint32_t k) const { return Seam{a, b, na, at + k}; }
-};
-
-GPK_HD uint32_t be16(const Seam& p) { return (uint32_t)p[0] << 8 | p[1]; }
+using gpk::Seam;  // gpk_seam.h
 
 // A gpk_tls being decoded, one dword per field (as dns::Msg)
 struct Msg {

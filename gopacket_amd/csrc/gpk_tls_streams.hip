@@ -2,11 +2,9 @@
 // (include/gpk_tls_streams.h): the step between gpk_tcpasm_batch's
 // contiguous stream bytes and the record rules of gpk_tls_rules.h.
 //
-//   init_kernel   one lane per possible stream: no cut, no Skip == -1 seen
-//   cut_kernel    one lane per chunk: an atomicMin per stream of the position of
-//                 the first chunk with Skip > 0 (where the logical buffer is
-//                 cut), and a flag for a chunk with Skip == -1. No lane scans its
-//                 stream's chunk table.
+//   init_kernel, cut_kernel (gpk_streams.h, as the tail_kernel and the stream's
+//                 View): where each stream's logical buffer is cut, and whether
+//                 it has a start
 //   size_kernel   one lane per stream: candidate, carried state, then the
 //                 framing walk in size mode; the stream entry with its state and
 //                 sizes
@@ -15,8 +13,7 @@
 //   emit_kernel   one lane per stream: the walk again, in store mode, when the
 //                 stream's whole range fits every capacity; the last stream
 //                 also writes counts
-//   tail_kernel   a wave looks at 64 streams, one per lane, and moves the tail of
-//                 each that has one with all its lanes (copy_bytes of gpk_copy.h)
+//   tail_kernel   the unfinished tails into the tail arena
 // The framing chain is serial: a header's position depends on the Length in
 // front of it. One lane walks a stream, at one dependent header read per
 // record. Only a stream's first record can straddle the carried tail and the
@@ -31,6 +28,7 @@
 #include "../../include/gpk_tls_streams.h"
 #include "gpk_copy.h"
 #include "gpk_devguard.h"
+#include "gpk_streams.h"
 #include "gpk_tls_rules.h"
 #include "gpk_workspace.h"
 
@@ -42,9 +40,19 @@ extern "C" __attribute__((visibility("hidden"))) int gpk_with_device_tables(
 
 namespace {
 
-constexpr int kBlk = 256;
-constexpr int kSlotTcp = 5;  // gpk_layout slot of TCP
-constexpr uint64_t kNoCut = ~0ull;
+// the pass as gpk_streams.h takes it
+struct TlsPass {
+  using In = gpk_tls_stream_in;
+  using Out = gpk_tls_stream_out;
+  using Stream = gpk_tls_stream;
+  static constexpr int32_t kLayer = GPK_LT_TLS;
+  static constexpr uint32_t kNew = GPK_TLSS_NEW, kSynced = GPK_TLSS_SYNCED, kNone = GPK_TLSS_NONE,
+                            kNostart = GPK_TLSS_NOSTART, kNState = GPK_TLSS_NSTATE;
+  static constexpr uint32_t kFrameUnstarted = GPK_TLSS_FRAME_UNSTARTED, kAllFlags = GPK_TLSS_ALL_FLAGS;
+  static constexpr uint32_t kDropped = GPK_TLSS_ST_DROPPED, kTooBig = GPK_TLSS_ST_TOOBIG,
+                            kBadTail = GPK_TLSS_ST_BADTAIL;
+};
+using Args = StreamArgs<TlsPass>;
 
 // what lies in front of a stream: record entries, failed ones, hello entries,
 // server name bytes, tail bytes, streams framed
@@ -57,25 +65,6 @@ struct TotAdd {
                a.framed + b.framed};
   }
 };
-
-struct Args {
-  const uint8_t* data;  // the batch
-  const uint64_t* offsets;
-  const gpk_layout* layouts;
-  const gpk::DevTables* tab;
-  uint64_t n;  // the batch's packets: no more streams exist
-  gpk_tcp_streams as;
-  gpk_tls_stream_in in;
-  gpk_tls_stream_out out;
-  uint64_t* cut;      // [n] offset of the first Skip > 0 inside the stream's bytes, or kNoCut
-  uint32_t* nostart;  // [n] 1: a chunk with Skip == -1
-  uint32_t* framed;   // [n] 1: the stream was framed in this call
-};
-
-GPK_HD uint32_t stream_count(const Args& a) {
-  const uint64_t s = a.as.counts[0];
-  return (uint32_t)(s < a.n ? s : a.n);
-}
 
 GPK_HD Tot own_of(const Args& a, uint32_t j) {
   const gpk_tls_stream& e = a.out.streams[j];
@@ -90,66 +79,6 @@ struct TotOf {  // of stream j; nothing past S
   }
 };
 using TotIn = hipcub::TransformInputIterator<Tot, TotOf, hipcub::CountingInputIterator<uint32_t>>;
-
-// A stream's logical buffer and what the call knows about it
-struct View {
-  const uint8_t* tail;  // tail_in bytes
-  const uint8_t* nb;    // the new bytes
-  uint32_t tail_in, len;  // len: tail_in + the new bytes in front of the cut
-  uint32_t state, status;
-  bool frame, lost, closed;
-};
-
-// TCP.NextLayerType() of the stream's creating packet (tcp.go:591-597)
-GPK_HD bool candidate(const Args& a, uint32_t j) {
-  const uint32_t p = a.as.stream_first[j];
-  if (p >= a.n) return false;
-  const uint32_t s = a.layouts[p].start[kSlotTcp], e = a.layouts[p].end[kSlotTcp];
-  if (s == GPK_LAYOUT_ABSENT || e < s || e - s < 20) return false;
-  return gpk::tun::port_type(a.tab->tcp_port, a.data + a.offsets[p] + s) == GPK_LT_TLS;
-}
-
-GPK_HD void resolve(const Args& a, uint32_t j, View& v) {
-  v.tail = v.nb = nullptr;
-  v.tail_in = v.len = v.status = 0;
-  v.frame = v.lost = v.closed = false;
-  const uint32_t st = j < a.in.n ? a.in.state[j] : (uint32_t)GPK_TLSS_NEW;
-  if (st != GPK_TLSS_NEW && st != GPK_TLSS_SYNCED) {  // final: kept
-    v.state = st < GPK_TLSS_NSTATE ? st : (uint32_t)GPK_TLSS_NONE;
-    return;
-  }
-  if (st == GPK_TLSS_NEW && !candidate(a, j)) {
-    v.state = GPK_TLSS_NONE;
-    return;
-  }
-  if (a.nostart[j] && !(a.in.flags & GPK_TLSS_FRAME_UNSTARTED)) {
-    v.state = GPK_TLSS_NOSTART;
-    return;
-  }
-  v.frame = true;
-  v.state = GPK_TLSS_SYNCED;
-  v.closed = a.as.stream_closed[j] != GPK_TCPASM_OPEN;
-  uint64_t tl = 0, to = 0;
-  if (st == GPK_TLSS_SYNCED) {
-    tl = a.in.tail_len[j];
-    to = a.in.tail_off[j];
-    if (tl && (to > a.in.tail_bytes || tl > a.in.tail_bytes - to)) v.status = GPK_TLSS_ST_BADTAIL;
-  }
-  const uint64_t d0 = a.as.stream_data0[j], d1 = a.as.stream_data0[j + 1];
-  uint64_t nbytes = d1 >= d0 ? d1 - d0 : 0;
-  const uint64_t c = a.cut[j];
-  v.lost = c != kNoCut;
-  if (v.lost && c < nbytes) nbytes = c;
-  if (d1 < d0 || d1 > a.as.data_cap || tl + nbytes >= (1ull << 32)) v.status |= GPK_TLSS_ST_TOOBIG;
-  if (v.status) {  // as a loss, and no byte is read
-    v.lost = true;
-    return;
-  }
-  v.tail = a.in.tails + to;
-  v.nb = a.as.data + d0;
-  v.tail_in = (uint32_t)tl;
-  v.len = (uint32_t)(tl + nbytes);
-}
 
 struct Framed {
   uint32_t state, consumed, tail_len, nrec, nfailed, nhello, sni_bytes;
@@ -280,40 +209,6 @@ GPK_HD bool emit_one(const Args& a, uint32_t j, uint32_t S, const Tot& t) {
   return f.tail_len != 0;
 }
 
-// where the tail of stream j lies: [consumed, tail_in) of the carried tail (n0 bytes at s0), then the new bytes
-// from max(consumed, tail_in) on (n1 bytes at s1)
-GPK_HD void tail_parts(const Args& a, uint32_t j, const uint8_t*& s0, uint32_t& n0, const uint8_t*& s1, uint32_t& n1) {
-  const gpk_tls_stream& e = a.out.streams[j];
-  n0 = e.consumed < e.tail_in ? e.tail_in - e.consumed : 0;
-  n1 = e.tail_len - n0;
-  s0 = n0 ? a.in.tails + a.in.tail_off[j] + e.consumed : nullptr;  // tail_in > 0: j < in.n
-  s1 = n1 ? a.as.data + a.as.stream_data0[j] + (e.consumed + n0 - e.tail_in) : nullptr;
-}
-
-__global__ void __launch_bounds__(kBlk) init_kernel(const Args a) {
-  const uint64_t j = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
-  if (j >= a.n) return;
-  a.cut[j] = kNoCut;
-  a.nostart[j] = 0;
-  a.framed[j] = 0;
-}
-
-__global__ void __launch_bounds__(kBlk) cut_kernel(const Args a) {
-  const uint64_t have = a.as.counts[1] < a.as.chunk_cap ? a.as.counts[1] : a.as.chunk_cap;
-  const uint64_t c = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
-  if (c >= have) return;
-  const int64_t skip = a.as.chunks[c].skip;
-  if (skip == 0) return;
-  const uint32_t j = a.as.chunks[c].stream;
-  if (j >= stream_count(a)) return;
-  if (skip < 0) {
-    a.nostart[j] = 1;
-  } else {
-    const uint64_t d0 = a.as.stream_data0[j], at = a.as.chunks[c].dst;
-    atomicMin((unsigned long long*)&a.cut[j], (unsigned long long)(at >= d0 ? at - d0 : 0));
-  }
-}
-
 __global__ void __launch_bounds__(kBlk) size_kernel(const Args a) {
   const uint64_t j = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
   if (j < stream_count(a)) size_one(a, (uint32_t)j);
@@ -325,28 +220,6 @@ __global__ void __launch_bounds__(kBlk) emit_kernel(const Args a, const Tot* sta
   if (j < S) emit_one(a, (uint32_t)j, S, starts[j]);
 }
 
-__global__ void __launch_bounds__(kBlk) tail_kernel(const Args a) {
-  const uint32_t S = stream_count(a);
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t base = ((uint64_t)blockIdx.x * (kBlk / 64) + (threadIdx.x >> 6)) * 64;
-  if (base >= S) return;
-  const uint64_t j = base + lane;
-  bool has = false;
-  if (j < S) {
-    const gpk_tls_stream& e = a.out.streams[j];
-    has = e.state == GPK_TLSS_SYNCED && e.tail_len && !(e.status & GPK_TLSS_ST_DROPPED);
-  }
-  for (uint64_t todo = __ballot(has); todo; todo &= todo - 1) {  // wave-uniform
-    const uint32_t k = (uint32_t)(base + __builtin_ctzll(todo));
-    const uint8_t *s0, *s1;
-    uint32_t n0, n1;
-    tail_parts(a, k, s0, n0, s1, n1);
-    uint8_t* dst = a.out.tails + a.out.streams[k].tail_off;
-    if (n0) gpk::copy_bytes(dst, s0, n0, lane);
-    if (n1) gpk::copy_bytes(dst + n0, s1, n1, lane);
-  }
-}
-
 bool bad_out(const gpk_tls_stream_out* o) {
   return !o || !o->streams || !o->counts || ((uintptr_t)o->streams & 7) || ((uintptr_t)o->recs & 7) ||
          ((uintptr_t)o->hellos & 7) || (o->rec_cap && !o->recs) || (o->hello_cap && !o->hellos) ||
@@ -355,30 +228,7 @@ bool bad_out(const gpk_tls_stream_out* o) {
 
 bool bad_args(const gpk_parser* p, const gpk_batch* b, const gpk_results* r, const gpk_tcp_streams* as,
               const gpk_tls_stream_in* in, const gpk_tls_stream_out* o) {
-  if (!p || !b || !r || !as || bad_out(o) || !as->counts) return true;
-  if (b->n >= (1ull << 32)) return true;
-  if (b->n && (!b->data || !b->offsets || !r->layouts || !as->chunks || !as->stream_first || !as->stream_closed ||
-               !as->stream_data0 || !as->data))
-    return true;
-  if (in) {
-    if ((in->flags & ~GPK_TLSS_ALL_FLAGS) || in->n > b->n) return true;
-    if (in->n && (!in->state || !in->tail_off || !in->tail_len)) return true;
-    if (in->tail_bytes && !in->tails) return true;
-  }
-  return false;
-}
-
-Args make_args(const gpk_batch* b, const gpk_results* r, const gpk_tcp_streams* as, const gpk_tls_stream_in* in,
-               const gpk_tls_stream_out* o) {
-  Args a{};
-  a.data = b->data;
-  a.offsets = b->offsets;
-  a.layouts = r->layouts;
-  a.n = b->n;
-  a.as = *as;
-  if (in) a.in = *in;
-  a.out = *o;
-  return a;
+  return bad_out(o) || bad_stream_args<TlsPass>(p, b, r, as, in);
 }
 
 }  // namespace
@@ -445,11 +295,11 @@ int launch_step(const gpk::DevTables* tab, void* arg) {
   hipStream_t s = l.s;
   a.tab = tab;
   const unsigned blocks = (unsigned)((a.n + kBlk - 1) / kBlk);
-  hipLaunchKernelGGL(init_kernel, dim3(blocks), dim3(kBlk), 0, s, a);
+  hipLaunchKernelGGL(init_kernel<TlsPass>, dim3(blocks), dim3(kBlk), 0, s, a);
   if (a.as.chunk_cap) {
     const uint64_t cb = (a.as.chunk_cap + kBlk - 1) / kBlk;
     if (cb >= (1ull << 31)) return GPK_EINVAL;
-    hipLaunchKernelGGL(cut_kernel, dim3((unsigned)cb), dim3(kBlk), 0, s, a);
+    hipLaunchKernelGGL(cut_kernel<TlsPass>, dim3((unsigned)cb), dim3(kBlk), 0, s, a);
   }
   hipLaunchKernelGGL(size_kernel, dim3(blocks), dim3(kBlk), 0, s, a);
   size_t tb = h->tmp_bytes;
@@ -458,7 +308,7 @@ int launch_step(const gpk::DevTables* tab, void* arg) {
       hipSuccess)
     return GPK_EHIP;
   hipLaunchKernelGGL(emit_kernel, dim3(blocks), dim3(kBlk), 0, s, a, (const Tot*)h->starts);
-  if (a.out.tail_cap) hipLaunchKernelGGL(tail_kernel, dim3(blocks), dim3(kBlk), 0, s, a);
+  if (a.out.tail_cap) hipLaunchKernelGGL(tail_kernel<TlsPass>, dim3(blocks), dim3(kBlk), 0, s, a);
   return hipGetLastError() == hipSuccess ? GPK_OK : GPK_EHIP;
 }
 
@@ -473,7 +323,7 @@ extern "C" int gpk_tls_streams(gpk_tls_stream_decoder* d, gpk_ctx* ctx, const gp
   hipStream_t s = (hipStream_t)stream;
   if (hipMemsetAsync(o->counts, 0, 12 * 8, s) != hipSuccess) return GPK_EHIP;
   if (b->n == 0) return GPK_OK;
-  Launch l{d, make_args(b, r, as, in, o), s};
+  Launch l{d, make_args<TlsPass>(b, r, as, in, o), s};
   l.a.cut = d->cut, l.a.nostart = d->nostart, l.a.framed = d->framed;
   return gpk_with_device_tables(ctx, parser, stream, launch_step, &l);
 }
@@ -484,7 +334,7 @@ extern "C" int gpk_tls_streams_host(const gpk_parser* parser, const gpk_batch* b
   if (bad_args(parser, b, r, as, in, o)) return GPK_EINVAL;
   for (int k = 0; k < 12; k++) o->counts[k] = 0;
   if (b->n == 0) return GPK_OK;
-  Args a = make_args(b, r, as, in, o);
+  Args a = make_args<TlsPass>(b, r, as, in, o);
   a.tab = gpk_parser_tables(parser);
   const uint32_t S = stream_count(a);
   if (S == 0) return GPK_OK;
@@ -493,29 +343,12 @@ extern "C" int gpk_tls_streams_host(const gpk_parser* parser, const gpk_batch* b
   a.framed = new (std::nothrow) uint32_t[S];
   int rc = GPK_ENOMEM;
   if (a.cut && a.nostart && a.framed) {
-    for (uint32_t j = 0; j < S; j++) a.cut[j] = kNoCut, a.nostart[j] = 0, a.framed[j] = 0;
-    const uint64_t have = as->counts[1] < as->chunk_cap ? as->counts[1] : as->chunk_cap;
-    for (uint64_t c = 0; c < have; c++) {  // cut_kernel
-      const gpk_tcp_chunk& ch = as->chunks[c];
-      if (ch.skip == 0 || ch.stream >= S) continue;
-      if (ch.skip < 0) {
-        a.nostart[ch.stream] = 1;
-      } else {
-        const uint64_t d0 = as->stream_data0[ch.stream], at = ch.dst >= d0 ? ch.dst - d0 : 0;
-        if (at < a.cut[ch.stream]) a.cut[ch.stream] = at;
-      }
-    }
+    host_cut(a, S);
     for (uint32_t j = 0; j < S; j++) size_one(a, j);
     Tot t{0, 0, 0, 0, 0, 0};
     for (uint32_t j = 0; j < S; j++) {
       const Tot own = own_of(a, j);
-      if (emit_one(a, j, S, t)) {
-        const uint8_t *s0, *s1;
-        uint32_t n0, n1;
-        tail_parts(a, j, s0, n0, s1, n1);
-        if (n0) memcpy(o->tails + t.tail, s0, n0);
-        if (n1) memcpy(o->tails + t.tail + n0, s1, n1);
-      }
+      if (emit_one(a, j, S, t)) host_tail(a, j, t.tail);
       t = TotAdd()(t, own);
     }
     rc = GPK_OK;

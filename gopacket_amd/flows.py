@@ -56,6 +56,13 @@ order. group_of[i] < 0 says why packet i has no key (GROUP_* codes).
                                            record boundaries, the unfinished tail, one entry per
                                            record and per ClientHello, and the server names
   TLSStreams(ctx, parser, n)               the same over a stream of batches, on a TCPAssembler
+  DNSStreamDecoder(max_streams, max_msgs).decode(...)
+                                           gpk_dns_streams (include/gpk_dns_streams.h): the DNS
+                                           messages of the streams Assembler.assemble laid out:
+                                           message boundaries by the two length bytes, the
+                                           unfinished tail, one entry per message, its questions
+                                           and records, and the decompressed names
+  DNSStreams(ctx, parser, n)               the same over a stream of batches, on a TCPAssembler
 """
 import ctypes
 
@@ -1357,25 +1364,28 @@ class TLSStreamResult:
         return [(s["id"], nm) for s in self.streams for nm in s["names"] if nm is not None]
 
 
-class TLSStreams:
-    """TLS over reassembled streams: a TCPAssembler and a TLSStreamDecoder
-    behind it, over a stream of device batches. The state and the unfinished
-    tail of every open stream are kept per global stream id; the tails stay on
-    the device. Every open connection is a stream of every call (it goes in as
-    a carried entry), so the tail arena of one call is the input arena of the
-    next. A closed stream's state is dropped."""
+class _StreamPass:
+    """What TLSStreams and DNSStreams share: a TCPAssembler in front and a
+    stream decoder behind it, over a stream of device batches. The state and
+    the unfinished tail of every open stream are kept per global stream id; the
+    tails stay on the device. Every open connection is a stream of every call
+    (it goes in as a carried entry), so the tail arena of one call is the input
+    arena of the next. A closed stream's state is dropped. A subclass names its
+    decoder (_new_decoder), the state of a new stream (_NEW) and decodes one
+    call (_decode)."""
+    _NEW = 0
 
     def __init__(self, ctx, parser, max_packets, max_pages=0, timed=False, frame_unstarted=False, device=0, keys=False):
         self.ctx, self.parser = ctx, parser
         self.asm = TCPAssembler(ctx, parser, max_packets, max_pages=max_pages, device=device, keys=keys, timed=timed)
-        self.decoder = TLSStreamDecoder(self.asm.max_packets, device)
         self.frame_unstarted = bool(frame_unstarted)
         self.device = device
+        self.decoder = self._new_decoder()
         self._state = {}    # global id -> (state, tail_off, tail_len) into _tails
         self._tails = None
 
     def feed(self, data, offsets, caplens, timestamps=None):
-        """One batch (as TCPAssembler.assemble). Returns a TLSStreamResult."""
+        """One batch (as TCPAssembler.assemble). Returns the pass's result object."""
         return self._decode(self.asm.assemble(data, offsets, caplens, timestamps))
 
     def flush_all(self):
@@ -1384,24 +1394,56 @@ class TLSStreams:
     def flush_older_than(self, t):
         return self._decode(self.asm.flush_older_than(t))
 
-    def _decode(self, res):
+    def _carry_in(self):
+        """(the assembler's last call, carry) for the decoder: what the call's
+        streams had after the call before, in stream order."""
         import numpy as np
         import torch
         last = self.asm._last
-        if last is None or not res["streams"]:
-            return TLSStreamResult([], [0] * 12, res)
         ids = last["ids"]
-        S = len(ids)
-        n = last["offsets"].numel()
-        if n > self.decoder.max_packets:  # the assembler grew its workspaces
+        if last["offsets"].numel() > self.decoder.max_packets:  # the assembler grew its workspaces
             self.decoder.close()
-            self.decoder = TLSStreamDecoder(self.asm.max_packets, self.device)
+            self.decoder = self._new_decoder()
         dev = last["offsets"].device
-        st = np.zeros((3, S), np.int64)
+        st = np.zeros((3, len(ids)), np.int64)
         for j, g in enumerate(ids):
-            st[:, j] = self._state.get(g, (_lib.TLSS_NEW, 0, 0))
+            st[:, j] = self._state.get(g, (self._NEW, 0, 0))
         carry = (torch.tensor(st[0], dtype=torch.int32, device=dev), torch.tensor(st[1], dtype=torch.int64, device=dev),
                  torch.tensor(st[2], dtype=torch.int32, device=dev), self._tails)
+        return last, carry
+
+    def _carry_out(self, ids, ent, assembled, tails):
+        """Keep what the call left: ent[j] is stream j's entry (state, tail_off, tail_len)."""
+        self._tails = tails
+        for g, e, a in zip(ids, ent, assembled):
+            if a["closed"] is not None:
+                self._state.pop(g, None)
+            else:
+                self._state[g] = (int(e["state"]), int(e["tail_off"]), int(e["tail_len"]))
+
+    def close(self):
+        self.asm.close()
+        self.decoder.close()
+
+
+class TLSStreams(_StreamPass):
+    """TLS over reassembled streams: a TCPAssembler and a TLSStreamDecoder
+    behind it, over a stream of device batches. The state and the unfinished
+    tail of every open stream are kept per global stream id; the tails stay on
+    the device. Every open connection is a stream of every call (it goes in as
+    a carried entry), so the tail arena of one call is the input arena of the
+    next. A closed stream's state is dropped."""
+    _NEW = _lib.TLSS_NEW
+
+    def _new_decoder(self):
+        return TLSStreamDecoder(self.asm.max_packets, self.device)
+
+    def _decode(self, res):
+        if self.asm._last is None or not res["streams"]:
+            return TLSStreamResult([], [0] * 12, res)
+        last, carry = self._carry_in()
+        ids = last["ids"]
+        S = len(ids)
         out = self.decoder.decode_all(self.ctx, self.parser, last["data"], last["offsets"], last["caplens"],
                                       last["records"], last["layouts"], last["out"], carry=carry,
                                       frame_unstarted=self.frame_unstarted, stream=last["stream"])
@@ -1411,7 +1453,6 @@ class TLSStreams:
         recs = out["recs"].cpu().numpy().view(_lib.TLS_STREAM_REC_DTYPE)
         hellos = out["hellos"].cpu().numpy().view(_lib.TLS_HELLO_DTYPE)
         snis = out["snis"].cpu().numpy()
-        self._tails = out["tails"]
         streams = []
         for j, (g, e, a) in enumerate(zip(ids, ent, res["streams"])):
             r0, h0 = int(e["rec0"]), int(e["hello0"])
@@ -1423,12 +1464,281 @@ class TLSStreams:
             if "key" in a:
                 d["key"] = a["key"]
             streams.append(d)
-            if a["closed"] is not None:
-                self._state.pop(g, None)
-            else:
-                self._state[g] = (int(e["state"]), int(e["tail_off"]), int(e["tail_len"]))
+        self._carry_out(ids, ent, res["streams"], out["tails"])
         return TLSStreamResult(streams, counts, res)
 
-    def close(self):
-        self.asm.close()
-        self.decoder.close()
+
+class DNSStreamDecoder(_Handle):
+    """gpk_dns_streams (include/gpk_dns_streams.h): the DNS messages of the
+    streams of one Assembler.assemble call. Owns the workspace of the scans for
+    calls of up to max_streams packets and msg_cap <= max_msgs message entries;
+    device=None makes a host-only one (decode_host).
+
+    The result is variable-length on two levels: streams[S] (DNS_STREAM_DTYPE)
+    name ranges of msgs[msg_cap] (DNS_STREAM_MSG_DTYPE, one per message) and of
+    the tail arena tails[tail_cap]; a stream whose range does not fit is not
+    written (DNSS_ST_DROPPED). A message names ranges of rrs[rr_cap]
+    (DNS_RR_DTYPE) and of the byte arena names[name_cap]; a message whose range
+    does not fit is not written (DNSS_MSG_DROPPED). counts tells what the call
+    needs (needed()); the rr and name needs are those of the placed messages,
+    so decode_all / decode_host_all size the streams first, then the messages,
+    and decode once more. `carry` is as for TLSStreamDecoder."""
+
+    _create, _destroy = "gpk_dns_stream_decoder_create", "gpk_dns_stream_decoder_destroy"
+    KEYS = ("streams", "msgs", "rrs", "names", "tails", "counts")
+    ASM_KEYS = TLSStreamDecoder.ASM_KEYS
+
+    def __init__(self, max_streams=1, max_msgs=None, device=0):
+        self.max_msgs = int(max_msgs if max_msgs is not None else max(4 * int(max_streams), 1024))
+        if device is None:  # host-only: no handle
+            self.h, self.max_packets = ctypes.c_void_p(), int(max_streams)
+            return
+        self.h = ctypes.c_void_p()
+        _lib.check(_lib.lib().gpk_dns_stream_decoder_create(ctypes.byref(self.h), int(device), int(max_streams),
+                                                            self.max_msgs))
+        self.max_packets = int(max_streams)
+
+    @staticmethod
+    def needed(counts):
+        """(message entries, rr entries, name bytes, tail bytes) the call needs, from counts[12]."""
+        return tuple(int(x) for x in counts[5:9])
+
+    @staticmethod
+    def _structs(ptr, numel, asm, carry, caps, out, frame_unstarted, max_message):
+        a = _lib.TcpStreams(*[ptr(asm[k]) if asm.get(k) is not None else None for k in DNSStreamDecoder.ASM_KEYS],
+                            int(asm.get("chunk_cap", numel(asm["chunks"]) // _lib.TCP_CHUNK_DTYPE.itemsize)),
+                            int(asm.get("data_cap", numel(asm["data"]))))
+        flags = _lib.DNSS_FRAME_UNSTARTED if frame_unstarted else 0
+        if carry is None:
+            i = _lib.DnsStreamIn(None, None, None, None, 0, 0, flags, int(max_message))
+        else:
+            state, off, ln, tails = carry
+            nt = 0 if tails is None else numel(tails)
+            i = _lib.DnsStreamIn(ptr(state), ptr(off), ptr(ln), ptr(tails) if nt else None, numel(state), nt, flags,
+                                 int(max_message))
+        o = _lib.DnsStreamOut(ptr(out["streams"]), *[ptr(out[k]) if c else None for k, c in
+                                                     zip(("msgs", "rrs", "names", "tails"), caps)],
+                              ptr(out["counts"]), *caps)
+        return a, i, o
+
+    def decode(self, ctx, parser, data, offsets, caplens, records, layouts, asm, msg_cap, rr_cap, name_cap, tail_cap,
+               carry=None, frame_unstarted=False, max_message=0, out=None, stream=None):
+        """Device tensors in: the batch the assembler was given, its records
+        and layouts, and `asm`, the dict Assembler.assemble returned for it.
+        Returns dict(streams[64 n] (uint8, _lib.DNS_STREAM_DTYPE), msgs[80
+        msg_cap] (uint8, _lib.DNS_STREAM_MSG_DTYPE), rrs[96 rr_cap],
+        names[name_cap], tails[tail_cap], counts[12] (int64)) of device tensors
+        (or fills `out`); stream entries at and past counts[0] are not written,
+        nor is anything past a capacity. Asynchronous on `stream`."""
+        import torch
+        caps = (int(msg_cap), int(rr_cap), int(name_cap), int(tail_cap))
+        n, dev = offsets.numel(), offsets.device
+        if out is None:
+            u8 = torch.uint8
+            out = dict(streams=torch.empty(max(n, 1) * 64, dtype=u8, device=dev),
+                       msgs=torch.empty(caps[0] * _lib.DNS_STREAM_MSG_DTYPE.itemsize, dtype=u8, device=dev),
+                       rrs=torch.empty(caps[1] * _lib.DNS_RR_DTYPE.itemsize, dtype=u8, device=dev),
+                       names=torch.empty(caps[2], dtype=u8, device=dev), tails=torch.empty(caps[3], dtype=u8, device=dev),
+                       counts=torch.zeros(12, dtype=torch.int64, device=dev))
+        a, i, o = self._structs(lambda t: t.data_ptr(), lambda t: t.numel(), asm, carry, caps, out, frame_unstarted,
+                                max_message)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        _lib.check(_lib.lib().gpk_dns_streams(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                                              ctypes.byref(i), ctypes.byref(o), _lib.stream_ptr(stream)))
+        return out
+
+    def decode_all(self, ctx, parser, data, offsets, caplens, records, layouts, asm, msg_cap=0, rr_cap=0, name_cap=0,
+                   tail_cap=0, carry=None, frame_unstarted=False, max_message=0, stream=None):
+        """decode with capacities that hold everything: a first call with the
+        capacities given and, while counts reports an overflow, another with
+        every capacity raised to what counts names: once for the streams'
+        message entries and tails, once more for the messages' entries and
+        names (at most three calls). Synchronizes on the counts. A call that
+        needs more than max_msgs message entries raises."""
+        caps = (int(msg_cap), int(rr_cap), int(name_cap), int(tail_cap))
+        for _ in range(3):
+            out = self.decode(ctx, parser, data, offsets, caplens, records, layouts, asm, *caps, carry=carry,
+                              frame_unstarted=frame_unstarted, max_message=max_message, stream=stream)
+            counts = out["counts"].cpu().tolist()
+            if not counts[4]:
+                break
+            caps = tuple(max(c, x) for c, x in zip(caps, self.needed(counts)))
+        return out
+
+    @classmethod
+    def decode_host(cls, parser, data, offsets, caplens, records, layouts, asm, msg_cap, rr_cap, name_cap, tail_cap,
+                    carry=None, frame_unstarted=False, max_message=0, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_dns_streams_host); asm holds the assembler's outputs as numpy
+        arrays (chunks as _lib.TCP_CHUNK_DTYPE, stream_first, stream_closed,
+        stream_data0, counts, data at least); `fill` is the byte the outputs
+        start with."""
+        import numpy as np
+        caps = (int(msg_cap), int(rr_cap), int(name_cap), int(tail_cap))
+        keep = (np.ascontiguousarray(data, np.uint8), np.ascontiguousarray(offsets, np.uint64),
+                np.ascontiguousarray(caplens, np.uint32), np.ascontiguousarray(records, _lib.RECORD_DTYPE),
+                np.ascontiguousarray(layouts, _lib.LAYOUT_DTYPE))
+        n = len(keep[2])
+        asm = dict(asm)
+        for k, dt in (("chunks", _lib.TCP_CHUNK_DTYPE), ("stream_first", np.uint32), ("stream_closed", np.uint32),
+                      ("stream_data0", np.uint64), ("counts", np.uint64), ("data", np.uint8)):
+            asm[k] = np.ascontiguousarray(asm[k], dt)
+        asm.setdefault("chunk_cap", len(asm["chunks"]))
+        asm.setdefault("data_cap", len(asm["data"]))
+        if carry is not None:
+            carry = (np.ascontiguousarray(carry[0], np.uint32), np.ascontiguousarray(carry[1], np.uint64),
+                     np.ascontiguousarray(carry[2], np.uint32),
+                     None if carry[3] is None else np.ascontiguousarray(carry[3], np.uint8))
+        out = dict(streams=np.empty(max(n, 1), _lib.DNS_STREAM_DTYPE), msgs=np.empty(caps[0], _lib.DNS_STREAM_MSG_DTYPE),
+                   rrs=np.empty(caps[1], _lib.DNS_RR_DTYPE), names=np.empty(caps[2], np.uint8),
+                   tails=np.empty(caps[3], np.uint8), counts=np.empty(12, np.uint64))
+        for v in out.values():
+            v.view(np.uint8)[:] = fill
+        a, i, o = cls._structs(lambda t: t.ctypes.data, lambda t: t.size, asm, carry, caps, out, frame_unstarted,
+                               max_message)
+        b = _lib.Batch(keep[0].ctypes.data, keep[1].ctypes.data, keep[2].ctypes.data, n, keep[0].size)
+        r = _lib.Results(keep[3].ctypes.data, None, None, keep[4].ctypes.data)
+        _lib.check(_lib.lib().gpk_dns_streams_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(a),
+                                                   ctypes.byref(i), ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def decode_host_all(cls, parser, data, offsets, caplens, records, layouts, asm, msg_cap=0, rr_cap=0, name_cap=0,
+                        tail_cap=0, carry=None, frame_unstarted=False, max_message=0):
+        """decode_host with the retries of decode_all."""
+        caps = (int(msg_cap), int(rr_cap), int(name_cap), int(tail_cap))
+        for _ in range(3):
+            out = cls.decode_host(parser, data, offsets, caplens, records, layouts, asm, *caps, carry=carry,
+                                  frame_unstarted=frame_unstarted, max_message=max_message)
+            if not int(out["counts"][4]):
+                break
+            caps = tuple(max(c, x) for c, x in zip(caps, cls.needed(out["counts"])))
+        return out
+
+
+class DNSStreamResult:
+    """What DNSStreams returns for one call. streams: [dict(id (global), state
+    (DNSS_*), status, tail_in, msgs (DNS_STREAM_MSG_DTYPE), closed, and key
+    with keys=True on a new stream)]; offsets of msgs and of their entries are
+    relative to the stream's logical buffer of this call (tail_in carried
+    bytes, then the new ones). counts: gpk_dns_stream_out.counts. rrs and names
+    are the call's arenas on the host. The streams' bytes stay on the device
+    until messages() asks for the logical buffers of the streams that have
+    decoded messages."""
+
+    def __init__(self, streams, counts, assembled, rrs=None, names=None, buffers=None):
+        self.streams, self.counts, self.assembled = streams, counts, assembled
+        self.rrs, self.names, self._buffers, self._bytes = rrs, names, buffers, None
+
+    @staticmethod
+    def _decoded(m):
+        return not int(m["status"]) and not int(m["msg"]["err"])
+
+    def _logical(self):
+        """{stream index: its logical buffer} for the streams with decoded messages: one device gather, one copy."""
+        if self._bytes is None:
+            import torch
+            self._bytes = {}
+            want = [j for j, s in enumerate(self.streams) if any(self._decoded(m) for m in s["msgs"])]
+            if want:
+                parts = [p for j in want for p in self._buffers(j)]
+                flat = torch.cat(parts).cpu().numpy().tobytes() if parts else b""
+                at = 0
+                for j in want:
+                    n = sum(p.numel() for p in self._buffers(j))
+                    self._bytes[j] = flat[at:at + n]
+                    at += n
+        return self._bytes
+
+    def messages(self):
+        """[(global stream id, layers.DNS)] of the messages that decoded, in stream and message order."""
+        from . import layers
+        out, bufs = [], self._logical()
+        for j, s in enumerate(self.streams):
+            for m in s["msgs"]:
+                if self._decoded(m):
+                    t = m["msg"]
+                    d = layers.DNS()
+                    d._from_record(t, self.rrs[int(t["rr0"]):int(t["rr0"]) + int(t["nrr"])], self.names, bufs[j])
+                    out.append((s["id"], d))
+        return out
+
+    def questions(self):
+        """[(global stream id, name, type)] of every question of the messages that decoded: from the tables and
+        the names alone, no stream byte."""
+        out = []
+        for s in self.streams:
+            for m in s["msgs"]:
+                if self._decoded(m):
+                    t = m["msg"]
+                    for r in self.rrs[int(t["rr0"]):int(t["rr0"]) + int(t["qdcount"])]:
+                        o = int(r["name_off"])
+                        out.append((s["id"], bytes(self.names[o:o + int(r["name_len"])]), int(r["type"])))
+        return out
+
+
+class DNSStreams(_StreamPass):
+    """DNS over reassembled streams: a TCPAssembler and a DNSStreamDecoder
+    behind it, over a stream of device batches; state and tails are carried as
+    _StreamPass describes. max_message (0: none) is gpk_dns_stream_in's
+    max_msg_len, the work cap for untrusted traffic: longer messages are framed
+    over and come back as DNSS_MSG_SKIPPED. The capacities a call needed are
+    kept as the first guess of the next, and the decoder grows with the number
+    of messages a call holds."""
+    _NEW = _lib.DNSS_NEW
+
+    def __init__(self, ctx, parser, max_packets, max_pages=0, timed=False, frame_unstarted=False, max_message=0,
+                 device=0, keys=False):
+        self.max_message = int(max_message)
+        self._max_msgs = max(4 * int(max_packets), 1024)
+        self._caps = (0, 0, 0, 0)
+        super().__init__(ctx, parser, max_packets, max_pages=max_pages, timed=timed, frame_unstarted=frame_unstarted,
+                         device=device, keys=keys)
+
+    def _new_decoder(self):
+        return DNSStreamDecoder(self.asm.max_packets, self._max_msgs, self.device)
+
+    def _decode(self, res):
+        if self.asm._last is None or not res["streams"]:
+            return DNSStreamResult([], [0] * 12, res)
+        last, carry = self._carry_in()
+        ids = last["ids"]
+        S = len(ids)
+        caps = tuple(min(c, m) for c, m in zip(self._caps, (self._max_msgs,) + (1 << 62,) * 3))
+        for _ in range(4):
+            out = self.decoder.decode(self.ctx, self.parser, last["data"], last["offsets"], last["caplens"],
+                                      last["records"], last["layouts"], last["out"], *caps, carry=carry,
+                                      frame_unstarted=self.frame_unstarted, max_message=self.max_message,
+                                      stream=last["stream"])
+            counts = out["counts"].cpu().tolist()
+            if not counts[4]:
+                break
+            need = DNSStreamDecoder.needed(counts)
+            if need[0] > self._max_msgs:  # more messages than the decoder's scans hold
+                self._max_msgs = 2 * need[0]
+                self.decoder.close()
+                self.decoder = self._new_decoder()
+            caps = tuple(max(c, x) for c, x in zip(caps, need))
+        self._caps = caps
+        self._last_call = dict(carry=carry, out=out, caps=caps)  # what went in beside asm._last, and what came out
+        ent = out["streams"].cpu().numpy().view(_lib.DNS_STREAM_DTYPE)[:S]
+        msgs = out["msgs"].cpu().numpy().view(_lib.DNS_STREAM_MSG_DTYPE)
+        rrs = out["rrs"].cpu().numpy().view(_lib.DNS_RR_DTYPE)
+        names = out["names"].cpu().numpy()
+        streams = []
+        for g, e, a in zip(ids, ent, res["streams"]):
+            m0 = int(e["msg0"])
+            d = dict(id=g, state=int(e["state"]), status=int(e["status"]), tail_in=int(e["tail_in"]),
+                     msgs=msgs[m0:m0 + int(e["nmsg"])], closed=a["closed"])
+            if "key" in a:
+                d["key"] = a["key"]
+            streams.append(d)
+        tails_in, toff = carry[3], carry[1].cpu().tolist()
+        data = last["out"]["data"]
+
+        def buffers(j):  # the device slices of stream j's logical buffer
+            a, t = res["streams"][j], streams[j]["tail_in"]
+            return ([tails_in[toff[j]:toff[j] + t]] if t else []) + [data[a["data0"]:a["data1"]]]
+        self._carry_out(ids, ent, res["streams"], out["tails"])
+        return DNSStreamResult(streams, counts, res, rrs, names, buffers)

@@ -22,6 +22,8 @@
  *   Slice       data is that payload. Over TCP it starts with the two length
  *               bytes, which the reference decodes as the ID (decodeDNS is
  *               the same function for both, dns.go:321-330); so does this.
+ *               gpk_dns_streams.h frames the messages of reassembled TCP
+ *               streams by those bytes and decodes each one whole.
  *   Loop        DNS sets BaseLayer{Contents: data} only and Payload() returns
  *               nil (dns.go:343,434-436): the reference's loop ends after it
  *               with nil. 107 is appended to the decoded list, nothing follows.

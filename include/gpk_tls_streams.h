@@ -74,8 +74,8 @@
  *               (GPK_TLSS_ST_BADTAIL).
  *
  * Out of scope: a ClientHello handshake message fragmented over several TLS
- * records, ServerHello and certificate decoding, DNS over TCP streams, DTLS
- * and QUIC. No gpk_tls_err value is added.
+ * records, ServerHello and certificate decoding, DTLS and QUIC (DNS over TCP
+ * streams is gpk_dns_streams.h). No gpk_tls_err value is added.
  *
  * Cost: one lane frames one stream, twice (sizes, then entries): one dependent
  * header read per record, not per byte. A single stream of very many records
