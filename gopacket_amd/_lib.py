@@ -127,6 +127,8 @@ EXPORTS = (
     "gpk_tls_stream_decoder_create", "gpk_tls_stream_decoder_destroy", "gpk_tls_streams", "gpk_tls_streams_host",
     # include/gpk_dns_streams.h
     "gpk_dns_stream_decoder_create", "gpk_dns_stream_decoder_destroy", "gpk_dns_streams", "gpk_dns_streams_host",
+    # include/gpk_ndp.h
+    "gpk_ndp_decoder_create", "gpk_ndp_decoder_destroy", "gpk_ndp_batch", "gpk_ndp_batch_host", "gpk_ndp_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -348,6 +350,44 @@ class Dnss(ctypes.Structure):
     _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
                 ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("rrs", ctypes.c_void_p),
                 ("names", ctypes.c_void_p), ("rr_cap", ctypes.c_uint64), ("name_cap", ctypes.c_uint64)]
+
+
+# include/gpk_ndp.h constants
+(LT_ICMPV6_ROUTER_SOLICITATION, LT_ICMPV6_ROUTER_ADVERTISEMENT, LT_ICMPV6_NEIGHBOR_SOLICITATION,
+ LT_ICMPV6_NEIGHBOR_ADVERTISEMENT, LT_ICMPV6_REDIRECT) = range(124, 129)
+LT_MLDV1_REPORT, LT_MLDV1_DONE, LT_MLDV1_QUERY, LT_MLDV2_REPORT, LT_MLDV2_QUERY = range(135, 140)
+(NDP_RS, NDP_RA, NDP_NS, NDP_NA, NDP_REDIRECT, NDP_MLD1_QUERY, NDP_MLD1_REPORT, NDP_MLD1_DONE, NDP_MLD2_QUERY,
+ NDP_MLD2_REPORT, NDP_ICMP6) = (1 << k for k in range(11))
+NDP_MESSAGES, NDP_ALL = 1023, 2047
+# layer type -> its bit of the kinds mask
+NDP_KIND_OF_TYPE = {
+    LT_ICMPV6_ROUTER_SOLICITATION: NDP_RS, LT_ICMPV6_ROUTER_ADVERTISEMENT: NDP_RA,
+    LT_ICMPV6_NEIGHBOR_SOLICITATION: NDP_NS, LT_ICMPV6_NEIGHBOR_ADVERTISEMENT: NDP_NA,
+    LT_ICMPV6_REDIRECT: NDP_REDIRECT, LT_MLDV1_QUERY: NDP_MLD1_QUERY, LT_MLDV1_REPORT: NDP_MLD1_REPORT,
+    LT_MLDV1_DONE: NDP_MLD1_DONE, LT_MLDV2_QUERY: NDP_MLD2_QUERY, LT_MLDV2_REPORT: NDP_MLD2_REPORT}
+NDP_NONE, NDP_UNKNOWN = -1, -2
+NDP_CLASS_OK, NDP_CLASS_FAILED = range(2)
+NDP_NCLASS = 2
+NDP_ERR_FIRST, NDP_ERR_END = 140, 155  # gpk_ndp_err: GPK_NDP_ERR_RS_SHORT .. GPK_NDP_ERR_RECORD_AUX
+(NDP_ERR_RS_SHORT, NDP_ERR_RA_SHORT, NDP_ERR_NS_SHORT, NDP_ERR_NA_SHORT, NDP_ERR_REDIRECT_SHORT, NDP_ERR_OPT_SHORT,
+ NDP_ERR_OPT_ZERO, NDP_ERR_OPT_OVERRUN, NDP_ERR_MLD1_SHORT, NDP_ERR_MLD2_QUERY_SHORT, NDP_ERR_MLD2_QUERY_SOURCES,
+ NDP_ERR_MLD2_REPORT_SHORT, NDP_ERR_RECORD_SHORT, NDP_ERR_RECORD_SOURCES, NDP_ERR_RECORD_AUX) = range(140, 155)
+NDP_ST_TRUNCATED, NDP_ST_DROPPED = 1, 2
+# gpk_ndp (64 B): one candidate's message
+NDP_DTYPE = np.dtype([
+    ("layer_type", "u1"), ("err", "u1"), ("status", "u1"), ("flags", "u1"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("hdr_off", "<u4"), ("len", "<u4"), ("contents_len", "<u4"), ("payload_off", "<u4"), ("payload_len", "<u4"),
+    ("v", "<u4", (4,)), ("entry0", "<u8"), ("nentries", "<u4"), ("count", "<u2"), ("s_qrv", "u1"), ("qqic", "u1")])
+# gpk_ndp_entry (16 B): one ICMPv6Option or one MLDv2MulticastAddressRecord
+NDP_ENTRY_DTYPE = np.dtype([
+    ("type", "u1"), ("aux_data_len", "u1"), ("n", "<u2"), ("off", "<u4"), ("ext", "<u4"), ("aux_off", "<u4")])
+
+
+class Ndps(ctypes.Structure):
+    """gpk_ndps: the outputs of gpk_ndp_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("entries", ctypes.c_void_p),
+                ("entry_cap", ctypes.c_uint64)]
 
 
 # include/gpk_tls.h constants
@@ -761,6 +801,11 @@ def lib():
         "gpk_dns_streams": ([vp, vp, vp, P(Batch), P(Results), P(TcpStreams), P(DnsStreamIn), P(DnsStreamOut), vp],
                             c_int),
         "gpk_dns_streams_host": ([vp, P(Batch), P(Results), P(TcpStreams), P(DnsStreamIn), P(DnsStreamOut)], c_int),
+        "gpk_ndp_decoder_create": ([P(vp), c_int, u64], c_int),
+        "gpk_ndp_decoder_destroy": ([vp], c_int),
+        "gpk_ndp_batch": ([vp, vp, vp, P(Batch), P(Results), u32, P(Ndps), vp], c_int),
+        "gpk_ndp_batch_host": ([vp, P(Batch), P(Results), u32, P(Ndps)], c_int),
+        "gpk_ndp_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

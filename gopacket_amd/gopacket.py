@@ -619,12 +619,15 @@ class DecodingLayerParser:
         inst = dlc._instances()
         self._decoders = {k: d for k, d in inst.items()
                           if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)
-                          and not getattr(d, "dns_kind", 0) and not getattr(d, "tls_kind", 0)}  # kind -> instance
+                          and not getattr(d, "dns_kind", 0) and not getattr(d, "tls_kind", 0)
+                          and not getattr(d, "ndp_kind", 0)}  # kind -> instance
         # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
         self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
         # layers.ICMPv4 / ICMPv6 / ICMPv6Echo / ARP: decoded after the six-layer decode (gpk_control_batch), by GPK_CTL_* kind
         self._controls = {d.control_kind: d for d in inst.values() if getattr(d, "control_kind", 0)}
-        # layers.DNS: decoded after the control pass (gpk_dns_batch)
+        # the ten NDP / MLD message layers: decoded after the control pass (gpk_ndp_batch), by GPK_NDP_* kind
+        self._ndps = {d.ndp_kind: d for d in inst.values() if getattr(d, "ndp_kind", 0)}
+        # layers.DNS: decoded after the NDP pass (gpk_dns_batch)
         self._dns = next((d for d in inst.values() if getattr(d, "dns_kind", 0)), None)
         # layers.TLS: decoded after the DNS pass (gpk_tls_batch)
         self._tls = next((d for d in inst.values() if getattr(d, "tls_kind", 0)), None)
@@ -664,8 +667,8 @@ class DecodingLayerParser:
         return self._ctx or _default_ctx()
 
     def _post_passes(self):
-        """Whether the parser holds a tunnel, control, DNS or TLS layer: DecodeBatch returns a TunnelBatchResult."""
-        return bool(self._tunnels or self._controls or self._dns is not None or self._tls is not None)
+        """Whether the parser holds a tunnel, control, NDP / MLD, DNS or TLS layer: DecodeBatch returns a TunnelBatchResult."""
+        return bool(self._tunnels or self._controls or self._ndps or self._dns is not None or self._tls is not None)
 
     def DecodeLayers(self, data, decoded):
         """Decode one packet on the GPU; fills the registered layers and the
@@ -695,8 +698,15 @@ class DecodingLayerParser:
         stopped in front of one; checksum=True also makes their
         VerifyChecksum on the device.
 
+        A parser that holds one of the ten NDP / MLD message layers
+        (layers.ICMPv6RouterSolicitation ... MLDv2MulticastListenerReportMessage)
+        does so as well: after the control pass the NDP pass (gpk_ndp_batch)
+        decodes the message behind every ICMPv6 header that leads to one of
+        them (or behind a table edit that does), on every tunnel level
+        (NDP(i)).
+
         A parser that holds layers.DNS returns a TunnelBatchResult as well:
-        after the control pass the DNS pass (gpk_dns_batch) decodes the
+        after the control and NDP passes the DNS pass (gpk_dns_batch) decodes the
         message of every packet whose decode stopped in front of
         LayerTypeDNS, on every tunnel level.
 
@@ -706,7 +716,7 @@ class DecodingLayerParser:
         LayerTypeTLS, on every tunnel level (TLS(i), SNIs())."""
         if self._post_passes():
             if fields:
-                raise ValueError("fields=True is not available for a parser with tunnel, control, DNS or TLS layers")
+                raise ValueError("fields=True is not available for a parser with tunnel, control, NDP, DNS or TLS layers")
             return TunnelBatchResult(self, batch, outputs, gre_checksum, checksum=checksum)
         cfg = self._config(outputs)
         if fields:
@@ -982,15 +992,17 @@ class TunnelPart:
     i.e. the level's own checksum and flow outputs; peel: gpk_tunnel_batch's
     outputs for it (host arrays), the tunnel headers found at its end;
     control: gpk_control_batch's outputs for it (host arrays), or None when
-    the parser holds no control layer; dns: gpk_dns_batch's outputs for it
+    the parser holds no control layer; ndp: gpk_ndp_batch's outputs for it
+    (host arrays: records and entries cut to what was written), or None when
+    the parser holds none of the NDP / MLD layers; dns: gpk_dns_batch's outputs for it
     (host arrays: records, rrs and names cut to what was written), or None
     when the parser holds no layers.DNS; tls: gpk_tls_batch's outputs for it
     (host arrays: records, recs, hellos and snis cut to what was written), or
     None when the parser holds no layers.TLS."""
 
-    def __init__(self, first, index, batch, result, peel, control=None, dns=None, tls=None):
+    def __init__(self, first, index, batch, result, peel, control=None, dns=None, tls=None, ndp=None):
         self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
-        self.control, self.dns, self.tls = control, dns, tls
+        self.control, self.dns, self.tls, self.ndp = control, dns, tls, ndp
 
 
 class TunnelBatchResult:
@@ -1010,6 +1022,10 @@ class TunnelBatchResult:
         self._ctl_kinds, self._ctl_checksum = 0, checksum
         for k in parser._controls:
             self._ctl_kinds |= k
+        # the NDP pass's kinds: the message layers held, and whether layers.ICMPv6 opens the way behind its header
+        self._ndp_kinds = _lib.NDP_ICMP6 if parser._ndps and _lib.CTL_ICMP6 in parser._controls else 0
+        for k in parser._ndps:
+            self._ndp_kinds |= k
         run = self._run_device if device else self._run_host
         run(outputs, kinds, gre_checksum)
 
@@ -1017,6 +1033,7 @@ class TunnelBatchResult:
         import copy
         p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
         p.first, p._tunnels, p._controls, p._dns, p._tls, p._cfg = LayerType(first), {}, {}, None, None, None
+        p._ndps = {}
         return p
 
     @staticmethod
@@ -1026,12 +1043,12 @@ class TunnelBatchResult:
                     counts=np.zeros(8, np.uint32), index=np.zeros(0, np.uint32), in_offsets=np.zeros(0, np.uint64),
                     in_caplens=np.zeros(0, np.uint32), tunnels=np.zeros(0, _lib.TUNNEL_DTYPE))
 
-    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None, tls=None):
+    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None, tls=None, ndp=None):
         if len(self.levels) <= level:
             self.levels.append([])
         p = self._clone(first)
         part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
-                          BatchResult(p, None, r), peel, control, dns, tls)
+                          BatchResult(p, None, r), peel, control, dns, tls, ndp)
         part.result.batch = part.batch
         self.levels[level].append(part)
         for pos, g in enumerate(index):
@@ -1057,7 +1074,7 @@ class TunnelBatchResult:
         return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
 
     def _run_host(self, outputs, kinds, gre_checksum):
-        from .flows import ControlDecoder, Detunneler, DNSDecoder, TLSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, TLSDecoder
         b = self.batch
         work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
         level = 0
@@ -1072,18 +1089,20 @@ class TunnelBatchResult:
                     if kinds else self._no_peel(len(index))
                 ctl = ControlDecoder.decode_host(b.data, offs, caps, r["records"], r["layouts"], cfg, self._ctl_kinds,
                                                  self._ctl_checksum) if self._ctl_kinds else None
+                ndp = NDPDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg,
+                                                 kinds=self._ndp_kinds) if self._ndp_kinds else None
                 dns = DNSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
                     if self.parser._dns is not None else None
                 tls = TLSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
                     if self.parser._tls is not None else None
-                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns, tls)
+                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns, tls, ndp)
                 for lt, js in self._next_work(part, level):
                     nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
             work, level = nxt, level + 1
 
     def _run_device(self, outputs, kinds, gre_checksum):
         import torch
-        from .flows import ControlDecoder, Detunneler, DNSDecoder, TLSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, TLSDecoder
         b = self.batch
         ctx = self.parser.ctx()
         dev = torch.device("cuda", ctx.device)
@@ -1092,6 +1111,7 @@ class TunnelBatchResult:
         data = torch.from_numpy(host).to(dev)
         det = Detunneler(max(len(b), 1), ctx.device) if kinds else None
         ctd = ControlDecoder(max(len(b), 1), ctx.device) if self._ctl_kinds else None
+        ndd = NDPDecoder(max(len(b), 1), ctx.device) if self._ndp_kinds else None
         dnd = DNSDecoder(max(len(b), 1), ctx.device) if self.parser._dns is not None else None
         tld = TLSDecoder(max(len(b), 1), ctx.device) if self.parser._tls is not None else None
         try:
@@ -1112,6 +1132,7 @@ class TunnelBatchResult:
                     out = det.peel(ctx, data, offs, caps, rec, lay, cfg, kinds, gre_checksum) if det else None
                     cout = ctd.decode(ctx, data, offs, caps, rec, lay, cfg, self._ctl_kinds, self._ctl_checksum) \
                         if ctd else None
+                    nout = ndd.decode_all(ctx, data, offs, caps, rec, lay, cfg, kinds=self._ndp_kinds) if ndd else None
                     dout = dnd.decode_all(ctx, data, offs, caps, rec, lay, cfg) if dnd else None
                     tout = tld.decode_all(ctx, data, offs, caps, rec, lay, cfg) if tld else None
                     torch.cuda.synchronize(dev)
@@ -1127,6 +1148,16 @@ class TunnelBatchResult:
                                    index=cout["index"][:cm].cpu().numpy().view(np.uint32),
                                    records=cout["records"][:cm * _lib.CONTROL_DTYPE.itemsize].cpu().numpy().view(
                                        _lib.CONTROL_DTYPE))
+                    ndp = None
+                    if nout is not None:
+                        nc = nout["counts"].cpu().numpy().view(np.uint32)
+                        ndp = dict(verdict=nout["verdict"].cpu().numpy(),
+                                   class_start=nout["class_start"].cpu().numpy().view(np.uint32), counts=nc,
+                                   index=nout["index"][:int(nc[0])].cpu().numpy().view(np.uint32),
+                                   records=nout["records"][:int(nc[0]) * _lib.NDP_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.NDP_DTYPE),
+                                   entries=nout["entries"][:NDPDecoder.needed(nc) * _lib.NDP_ENTRY_DTYPE.itemsize]
+                                   .cpu().numpy().view(_lib.NDP_ENTRY_DTYPE))
                     dns = None
                     if dout is not None:
                         dc = dout["counts"].cpu().numpy().view(np.uint32)
@@ -1155,7 +1186,7 @@ class TunnelBatchResult:
                                    snis=tout["snis"][:need_sni].cpu().numpy())
                     if out is None:
                         self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls)
+                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls, ndp)
                         continue
                     m = int(out["counts"][0].item())
                     pl = dict(verdict=out["verdict"].cpu().numpy(),
@@ -1167,7 +1198,7 @@ class TunnelBatchResult:
                               tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
                                   _lib.TUNNEL_DTYPE))
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls)
+                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls, ndp)
                     for lt, js in self._next_work(part, level):
                         if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
                             io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
@@ -1177,7 +1208,7 @@ class TunnelBatchResult:
                         nxt.append((lt, index[pl["index"][js]], io, ic))
                 work, level = nxt, level + 1
         finally:
-            for h in (det, ctd, dnd, tld):
+            for h in (det, ctd, ndd, dnd, tld):
                 if h is not None:
                     h.close()
 
@@ -1198,6 +1229,28 @@ class TunnelBatchResult:
             return None
         v = int(part.control["verdict"][pos])
         return part.control["records"][v] if v >= 0 else None
+
+    def _ndp(self, part, pos):
+        """The gpk_ndp record of a part's packet, or None: not a candidate."""
+        if part.ndp is None:
+            return None
+        v = int(part.ndp["verdict"][pos])
+        return part.ndp["records"][v] if v >= 0 else None
+
+    @staticmethod
+    def _ndp_entries(part, t):
+        e0 = int(t["entry0"])
+        return part.ndp["entries"][e0:e0 + int(t["nentries"])]
+
+    def NDP(self, i):
+        """(the gpk_ndp record (NDP_DTYPE), its gpk_ndp_entry descriptors
+        (NDP_ENTRY_DTYPE): options, or multicast address records) of packet
+        i, or None: not a candidate. A failed message has no entries."""
+        part, pos = self._chain[i][-1]
+        t = self._ndp(part, pos)
+        if t is None:
+            return None
+        return t, self._ndp_entries(part, t)
 
     def _dns(self, part, pos):
         """The gpk_dns record of a part's packet, or None: not a candidate."""
@@ -1271,6 +1324,9 @@ class TunnelBatchResult:
             c = self._control(part, pos)
             if c is not None:
                 out += [LayerType(int(x)) for x in c["layer_types"][:int(c["nlayers"])]]
+            m = self._ndp(part, pos)
+            if m is not None and not int(m["err"]):
+                out.append(LayerType(int(m["layer_type"])))
             d = self._dns(part, pos)
             if d is not None and not int(d["err"]):
                 out.append(LayerType(_lib.LT_DNS))
@@ -1286,6 +1342,8 @@ class TunnelBatchResult:
             c = self._control(part, pos)
             d = self._dns(part, pos)
             s = self._tls(part, pos)
+            m = self._ndp(part, pos)
+            tr = tr or (m is not None and bool(int(m["status"]) & _lib.NDP_ST_TRUNCATED))
             tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED)) \
                 or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED)) \
                 or (d is not None and bool(int(d["status"]) & _lib.DNS_ST_TRUNCATED)) \
@@ -1314,6 +1372,13 @@ class TunnelBatchResult:
             if int(d["err"]):
                 buf = ctypes.create_string_buffer(256)
                 _lib.lib().gpk_dns_format_error(int(d["err"]), int(d["err_a0"]), int(d["err_a1"]), buf, 256)
+                return GoError(buf.value.decode())
+            return None
+        m = self._ndp(part, pos)
+        if m is not None:  # every one of the ten ends the loop: its error, or nil
+            if int(m["err"]):
+                buf = ctypes.create_string_buffer(256)
+                _lib.lib().gpk_ndp_format_error(int(m["err"]), int(m["err_a0"]), int(m["err_a1"]), buf, 256)
                 return GoError(buf.value.decode())
             return None
         if c is not None:  # the control layers' loop ended the decode: its error, the type it returned, or nil
@@ -1363,6 +1428,10 @@ class TunnelBatchResult:
                 elif int(c["nlayers"]) > 1:  # gopacket.Payload
                     o = int(c["payload_off"])
                     p._decoders[_lib.DEC_PAYLOAD]._hydrate(pkt[o:o + int(c["payload_len"])])
+            m = self._ndp(part, pos)
+            if m is not None and not int(m["err"]):
+                p._ndps[_lib.NDP_KIND_OF_TYPE[int(m["layer_type"])]]._from_record(
+                    m, self._ndp_entries(part, m), part.batch.packet(pos))
             d = self._dns(part, pos)
             if d is not None and not int(d["err"]):
                 r0 = int(d["rr0"])

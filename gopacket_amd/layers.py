@@ -1551,6 +1551,331 @@ class ARP(_ControlLayer):
         self.Contents, self.Payload = pkt[h:h + c], pkt[h + c:h + c + int(t["payload_len"])]
 
 
+# ---- layers/icmp6msg.go, mldv1.go, mldv2.go: the messages behind ICMPv6 ---------------
+# A DecodingLayerParser that holds one of these decodes them on the device after
+# the control pass (gpk_ndp_batch); the structs are filled from the packet's
+# gpk_ndp record, its gpk_ndp_entry descriptors and the packet's bytes
+# (_from_record). Every message is decoded into a fresh struct: the lists are
+# the message's own (include/gpk_ndp.h, Scope decisions). A time.Duration is an
+# int of nanoseconds.
+_SECOND, _MILLISECOND = 1000000000, 1000000
+
+
+class ICMPv6Opt(int):
+    """icmp6msg.go:24-60, 120-137"""
+
+    def String(self):
+        return _ICMPV6_OPT_NAMES.get(int(self), "Unknown(%d)" % int(self))
+
+
+(ICMPv6OptSourceAddress, ICMPv6OptTargetAddress, ICMPv6OptPrefixInfo, ICMPv6OptRedirectedHeader, ICMPv6OptMTU) = (
+    ICMPv6Opt(k) for k in range(1, 6))
+ICMPv6OptRecursiveDNSServer = ICMPv6Opt(25)
+_ICMPV6_OPT_NAMES = {1: "SourceAddress", 2: "TargetAddress", 3: "PrefixInfo", 4: "RedirectedHeader", 5: "MTU",
+                     25: "RecursiveDNSServer"}
+
+
+class ICMPv6Option:
+    """icmp6msg.go:111-115"""
+
+    def __init__(self, Type=0, Data=b""):
+        self.Type, self.Data = ICMPv6Opt(Type), bytes(Data)
+
+    def __eq__(self, o):
+        return isinstance(o, ICMPv6Option) and (int(self.Type), self.Data) == (int(o.Type), o.Data)
+
+    def __repr__(self):
+        return "ICMPv6Option(%s, %r)" % (self.Type.String(), self.Data)
+
+
+class ICMPv6Options(list):
+    """icmp6msg.go:118"""
+
+
+class _NDPLayer(BaseLayer):
+    _lt = None
+
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("NDP and MLD layers decode through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+    def LayerType(self):
+        return self._lt
+
+    def CanDecode(self):
+        return LayerClass([self._lt])
+
+    def NextLayerType(self):
+        return LayerTypePayload
+
+    def _base(self, t, pkt):
+        """BaseLayer from the record's ranges; the options of the entries."""
+        h = int(t["hdr_off"])
+        self.Contents = pkt[h:h + int(t["contents_len"])]
+        o = int(t["payload_off"])
+        self.Payload = pkt[o:o + int(t["payload_len"])]
+
+    @staticmethod
+    def _options(entries, pkt):
+        return ICMPv6Options(ICMPv6Option(int(e["type"]), pkt[int(e["off"]):int(e["off"]) + int(e["ext"])])
+                             for e in entries)
+
+    @staticmethod
+    def _ip(t, k, pkt):
+        return pkt[int(t["v"][k]):int(t["v"][k]) + 16]
+
+
+class ICMPv6RouterSolicitation(_NDPLayer):
+    """icmp6msg.go:69-73, 180-224. DecodeFromBytes sets no BaseLayer."""
+    kind = 400 + 0
+    ndp_kind = _lib.NDP_RS
+    _lt = LayerTypeICMPv6RouterSolicitation
+
+    def __init__(self):
+        self.Options = ICMPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.Options = self._options(entries, pkt)
+
+
+class ICMPv6RouterAdvertisement(_NDPLayer):
+    """icmp6msg.go:75-84, 226-293"""
+    kind = 400 + 1
+    ndp_kind = _lib.NDP_RA
+    _lt = LayerTypeICMPv6RouterAdvertisement
+
+    def __init__(self):
+        self.HopLimit = self.Flags = self.RouterLifetime = self.ReachableTime = self.RetransTimer = 0
+        self.Options = ICMPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        v = t["v"]
+        self.ReachableTime, self.RetransTimer, self.RouterLifetime, self.HopLimit = (int(x) for x in v)
+        self.Flags = int(t["flags"])
+        self.Options = self._options(entries, pkt)
+
+    def ManagedAddressConfig(self):
+        return self.Flags & 0x80 != 0
+
+    def OtherConfig(self):
+        return self.Flags & 0x40 != 0
+
+
+class ICMPv6NeighborSolicitation(_NDPLayer):
+    """icmp6msg.go:86-92, 295-342"""
+    kind = 400 + 2
+    ndp_kind = _lib.NDP_NS
+    _lt = LayerTypeICMPv6NeighborSolicitation
+
+    def __init__(self):
+        self.TargetAddress = b""
+        self.Options = ICMPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.TargetAddress = self._ip(t, 0, pkt)
+        self.Options = self._options(entries, pkt)
+
+
+class ICMPv6NeighborAdvertisement(_NDPLayer):
+    """icmp6msg.go:94-100, 344-409"""
+    kind = 400 + 3
+    ndp_kind = _lib.NDP_NA
+    _lt = LayerTypeICMPv6NeighborAdvertisement
+
+    def __init__(self):
+        self.Flags = 0
+        self.TargetAddress = b""
+        self.Options = ICMPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.Flags = int(t["flags"])
+        self.TargetAddress = self._ip(t, 0, pkt)
+        self.Options = self._options(entries, pkt)
+
+    def Router(self):
+        return self.Flags & 0x80 != 0
+
+    def Solicited(self):
+        return self.Flags & 0x40 != 0
+
+    def Override(self):
+        return self.Flags & 0x20 != 0
+
+
+class ICMPv6Redirect(_NDPLayer):
+    """icmp6msg.go:102-109, 411-460"""
+    kind = 400 + 4
+    ndp_kind = _lib.NDP_REDIRECT
+    _lt = LayerTypeICMPv6Redirect
+
+    def __init__(self):
+        self.TargetAddress = self.DestinationAddress = b""
+        self.Options = ICMPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.TargetAddress, self.DestinationAddress = self._ip(t, 0, pkt), self._ip(t, 1, pkt)
+        self.Options = self._options(entries, pkt)
+
+
+class MLDv1Message(_NDPLayer):
+    """mldv1.go:20-48. DecodeFromBytes sets no BaseLayer; NextLayerType is LayerTypeZero."""
+
+    def __init__(self):
+        self.MaximumResponseDelay = 0  # time.Duration: nanoseconds
+        self.MulticastAddress = b""
+
+    def NextLayerType(self):
+        return LayerType(0)  # gopacket.LayerTypeZero
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.MaximumResponseDelay = int(t["v"][2]) * _MILLISECOND
+        self.MulticastAddress = self._ip(t, 0, pkt)
+
+
+class MLDv1MulticastListenerQueryMessage(MLDv1Message):
+    """mldv1.go:87-132: Payload is data[20:] of a message longer than 20 bytes."""
+    kind = 400 + 5
+    ndp_kind = _lib.NDP_MLD1_QUERY
+    _lt = LayerTypeMLDv1MulticastListenerQuery
+
+    def IsGeneralQuery(self):
+        return self.MulticastAddress == bytes(16)
+
+    def IsSpecificQuery(self):
+        return not self.IsGeneralQuery()
+
+
+class MLDv1MulticastListenerReportMessage(MLDv1Message):
+    """mldv1.go:134-150"""
+    kind = 400 + 6
+    ndp_kind = _lib.NDP_MLD1_REPORT
+    _lt = LayerTypeMLDv1MulticastListenerReport
+
+
+class MLDv1MulticastListenerDoneMessage(MLDv1Message):
+    """mldv1.go:152-167"""
+    kind = 400 + 7
+    ndp_kind = _lib.NDP_MLD1_DONE
+    _lt = LayerTypeMLDv1MulticastListenerDone
+
+
+class MLDv2MulticastListenerQueryMessage(_NDPLayer):
+    """mldv2.go:34-257. DecodeFromBytes sets no BaseLayer; NextLayerType is LayerTypeZero."""
+    kind = 400 + 8
+    ndp_kind = _lib.NDP_MLD2_QUERY
+    _lt = LayerTypeMLDv2MulticastListenerQuery
+
+    def __init__(self):
+        self.MaximumResponseCode = 0
+        self.MulticastAddress = b""
+        self.SuppressRoutersideProcessing = False
+        self.QueriersRobustnessVariable = self.QueriersQueryIntervalCode = self.NumberOfSources = 0
+        self.SourceAddresses = []
+
+    def NextLayerType(self):
+        return LayerType(0)  # gopacket.LayerTypeZero
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.MaximumResponseCode = int(t["v"][2])
+        self.MulticastAddress = self._ip(t, 0, pkt)
+        self.SuppressRoutersideProcessing = bool(int(t["s_qrv"]) & 8)
+        self.QueriersRobustnessVariable = int(t["s_qrv"]) & 7
+        self.QueriersQueryIntervalCode = int(t["qqic"])
+        self.NumberOfSources = int(t["count"])
+        a = int(t["hdr_off"]) + 24
+        self.SourceAddresses = [pkt[a + 16 * k:a + 16 * k + 16] for k in range(self.NumberOfSources)]
+
+    def IsGeneralQuery(self):
+        return self.MulticastAddress == bytes(16)
+
+    def IsSpecificQuery(self):
+        return not self.IsGeneralQuery()
+
+    def QQI(self):
+        """mldv2.go:194-203, its uint16 arithmetic included: 0x1000 << (exp + 3) keeps its low 16 bits."""
+        data = self.QueriersQueryIntervalCode
+        if data < 128:
+            return _SECOND * data
+        exp, mant = (data & 0x70) >> 4, data & 0x0F
+        return _SECOND * ((mant | 0x1000 << (exp + 3)) & 0xFFFF)
+
+    def MaximumResponseDelay(self):
+        """mldv2.go:248-257 as written: a code below 0x8000 is returned as that
+        many nanoseconds, and the shift is made in 16 bits."""
+        code = self.MaximumResponseCode
+        if code < 0x8000:
+            return code
+        exp, mant = (code & 0x7000) >> 12, code & 0x0FFF
+        return _MILLISECOND * ((mant | 0x1000 << (exp + 3)) & 0xFFFF)
+
+
+class MLDv2MulticastAddressRecordType(int):
+    """mldv2.go:394-452"""
+
+    def String(self):
+        return _MLDV2_RECORD_NAMES.get(int(self), "UNKNOWN(%d)" % int(self))
+
+
+(MLDv2MulticastAddressRecordTypeModeIsIncluded, MLDv2MulticastAddressRecordTypeModeIsExcluded,
+ MLDv2MulticastAddressRecordTypeChangeToIncludeMode, MLDv2MulticastAddressRecordTypeChangeToExcludeMode,
+ MLDv2MulticastAddressRecordTypeAllowNewSources, MLDv2MulticastAddressRecordTypeBlockOldSources) = (
+    MLDv2MulticastAddressRecordType(k) for k in range(1, 7))
+_MLDV2_RECORD_NAMES = {1: "MODE_IS_INCLUDE", 2: "MODE_IS_EXCLUDE", 3: "CHANGE_TO_INCLUDE_MODE",
+                       4: "CHANGE_TO_EXCLUDE_MODE", 5: "ALLOW_NEW_SOURCES", 6: "BLOCK_OLD_SOURCES"}
+
+
+class MLDv2MulticastAddressRecord:
+    """mldv2.go:454-470"""
+
+    def __init__(self, RecordType=0, AuxDataLen=0, N=0, MulticastAddress=b"", SourceAddresses=(), AuxiliaryData=b""):
+        self.RecordType, self.AuxDataLen, self.N = MLDv2MulticastAddressRecordType(RecordType), AuxDataLen, N
+        self.MulticastAddress, self.SourceAddresses = bytes(MulticastAddress), list(SourceAddresses)
+        self.AuxiliaryData = bytes(AuxiliaryData)
+
+    def _key(self):
+        return (int(self.RecordType), self.AuxDataLen, self.N, self.MulticastAddress, self.SourceAddresses,
+                self.AuxiliaryData)
+
+    def __eq__(self, o):
+        return isinstance(o, MLDv2MulticastAddressRecord) and self._key() == o._key()
+
+    def __repr__(self):
+        return "MLDv2MulticastAddressRecord%r" % (self._key(),)
+
+
+class MLDv2MulticastListenerReportMessage(_NDPLayer):
+    """mldv2.go:297-392. DecodeFromBytes sets no BaseLayer."""
+    kind = 400 + 9
+    ndp_kind = _lib.NDP_MLD2_REPORT
+    _lt = LayerTypeMLDv2MulticastListenerReport
+
+    def __init__(self):
+        self.NumberOfMulticastAddressRecords = 0
+        self.MulticastAddressRecords = []
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        self.NumberOfMulticastAddressRecords = int(t["count"])
+        self.MulticastAddressRecords = []
+        for e in entries:
+            a, s, x, n = int(e["off"]), int(e["ext"]), int(e["aux_off"]), int(e["n"])
+            self.MulticastAddressRecords.append(MLDv2MulticastAddressRecord(
+                int(e["type"]), int(e["aux_data_len"]), n, pkt[a:a + 16], [pkt[s + 16 * k:s + 16 * k + 16] for k in range(n)],
+                pkt[x:x + 4 * int(e["aux_data_len"])]))
+
+
+NDP_LAYERS = (ICMPv6RouterSolicitation, ICMPv6RouterAdvertisement, ICMPv6NeighborSolicitation,
+              ICMPv6NeighborAdvertisement, ICMPv6Redirect, MLDv1MulticastListenerQueryMessage,
+              MLDv1MulticastListenerReportMessage, MLDv1MulticastListenerDoneMessage,
+              MLDv2MulticastListenerQueryMessage, MLDv2MulticastListenerReportMessage)
+
+
 # ---- layers/dns.go ------------------------------------------------------------------
 # A DecodingLayerParser that holds layers.DNS decodes the messages on the device
 # after the six-layer decode and the control pass (gpk_dns_batch); the struct is
