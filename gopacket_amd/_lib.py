@@ -129,6 +129,8 @@ EXPORTS = (
     "gpk_dns_stream_decoder_create", "gpk_dns_stream_decoder_destroy", "gpk_dns_streams", "gpk_dns_streams_host",
     # include/gpk_ndp.h
     "gpk_ndp_decoder_create", "gpk_ndp_decoder_destroy", "gpk_ndp_batch", "gpk_ndp_batch_host", "gpk_ndp_format_error",
+    # include/gpk_svc.h
+    "gpk_svc_decoder_create", "gpk_svc_decoder_destroy", "gpk_svc_batch", "gpk_svc_batch_host", "gpk_svc_format_error",
 )
 
 BPF_INSN_DTYPE = np.dtype([("code", "<u2"), ("jt", "u1"), ("jf", "u1"), ("k", "<u4")])
@@ -385,6 +387,35 @@ NDP_ENTRY_DTYPE = np.dtype([
 
 class Ndps(ctypes.Structure):
     """gpk_ndps: the outputs of gpk_ndp_batch."""
+    _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
+                ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("entries", ctypes.c_void_p),
+                ("entry_cap", ctypes.c_uint64)]
+
+
+# include/gpk_svc.h constants
+LT_NTP, LT_DHCPV4, LT_DHCPV6 = 117, 118, 134
+SVC_DHCP4, SVC_DHCP6, SVC_NTP = 1, 2, 4
+SVC_ALL = 7
+SVC_KIND_OF_TYPE = {LT_DHCPV4: SVC_DHCP4, LT_DHCPV6: SVC_DHCP6, LT_NTP: SVC_NTP}  # layer type -> its bit of the kinds mask
+SVC_NONE, SVC_UNKNOWN = -1, -2
+SVC_CLASS_OK, SVC_CLASS_FAILED = range(2)
+SVC_NCLASS = 2
+SVC_ERR_FIRST, SVC_ERR_END = 160, 170  # gpk_svc_err: GPK_SVC_ERR_DHCP4_SHORT .. GPK_SVC_ERR_NTP_SHORT
+(SVC_ERR_DHCP4_SHORT, SVC_ERR_DHCP4_HLEN, SVC_ERR_DHCP4_MAGIC, SVC_ERR_DHCP4_OPT_SHORT, SVC_ERR_DHCP4_OPT_MALFORMED,
+ SVC_ERR_DHCP6_SHORT, SVC_ERR_DHCP6_RELAY_SHORT, SVC_ERR_DHCP6_OPT_SHORT, SVC_ERR_DHCP6_OPT_LENGTH,
+ SVC_ERR_NTP_SHORT) = range(160, 170)
+SVC_ST_TRUNCATED, SVC_ST_DROPPED = 1, 2
+# gpk_svc (64 B): one candidate's message
+SVC_DTYPE = np.dtype([
+    ("layer_type", "u1"), ("err", "u1"), ("status", "u1"), ("reserved", "u1"), ("err_a0", "<u4"), ("err_a1", "<u4"),
+    ("hdr_off", "<u4"), ("len", "<u4"), ("contents_len", "<u4"), ("entry0", "<u8"), ("nentries", "<u4"),
+    ("b", "u1", (4,)), ("v", "<u4", (6,))])
+# gpk_svc_entry (8 B): one DHCPOption or one DHCPv6Option
+SVC_ENTRY_DTYPE = np.dtype([("code", "<u2"), ("length", "<u2"), ("off", "<u4")])
+
+
+class Svcs(ctypes.Structure):
+    """gpk_svcs: the outputs of gpk_svc_batch."""
     _fields_ = [("verdict", ctypes.c_void_p), ("class_start", ctypes.c_void_p), ("index", ctypes.c_void_p),
                 ("records", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("entries", ctypes.c_void_p),
                 ("entry_cap", ctypes.c_uint64)]
@@ -806,6 +837,11 @@ def lib():
         "gpk_ndp_batch": ([vp, vp, vp, P(Batch), P(Results), u32, P(Ndps), vp], c_int),
         "gpk_ndp_batch_host": ([vp, P(Batch), P(Results), u32, P(Ndps)], c_int),
         "gpk_ndp_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
+        "gpk_svc_decoder_create": ([P(vp), c_int, u64], c_int),
+        "gpk_svc_decoder_destroy": ([vp], c_int),
+        "gpk_svc_batch": ([vp, vp, vp, P(Batch), P(Results), u32, P(Svcs), vp], c_int),
+        "gpk_svc_batch_host": ([vp, P(Batch), P(Results), u32, P(Svcs)], c_int),
+        "gpk_svc_format_error": ([ctypes.c_uint, u32, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_create": ([P(vp), vp, u32, ctypes.c_char_p, ctypes.c_size_t], c_int),
         "gpk_bpf_destroy": ([vp], c_int),
         "gpk_bpf_run": ([vp, P(Batch), vp, vp, vp], c_int),

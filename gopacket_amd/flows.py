@@ -1201,6 +1201,89 @@ class NDPDecoder(_PostPass):
         return out
 
 
+class ServiceDecoder(_PostPass):
+    """gpk_svc_batch (include/gpk_svc.h): the DHCPv4, DHCPv6 and NTP
+    messages at the end of a decoded device batch. Owns the workspace of the
+    scans for up to max_packets packets; device=None makes a host-only one
+    (decode_host).
+
+    The result is variable-length: records[m] (SVC_DTYPE) name ranges of
+    entries[entry_cap] (SVC_ENTRY_DTYPE), one per DHCP option. A message
+    whose range does not fit is not written (SVC_ST_DROPPED); counts tells
+    what the batch needs (needed()), and
+    decode_all / decode_host_all size first and decode once more with exactly
+    that."""
+
+    _create, _destroy = "gpk_svc_decoder_create", "gpk_svc_decoder_destroy"
+    _Out = _lib.Svcs
+    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
+               ("records", lambda n: n, _lib.SVC_DTYPE), ("counts", lambda n: 8, "u4"))
+    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("entries",)
+
+    @staticmethod
+    def needed(counts):
+        """The entries the batch needs, from counts[8] (uint32)."""
+        c = [int(x) & 0xffffffff for x in counts]
+        return c[4] | c[5] << 32
+
+    def decode(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.SVC_ALL, out=None,
+               stream=None):
+        """Device tensors in: the batch (data 16-byte aligned), and the records
+        and layouts of ctx.decode_device(parser, ...) for it. kinds: SVC_* mask
+        of the layers the caller's parser holds. Returns dict(verdict[n],
+        class_start[3], index[n], records[64 n] (uint8, _lib.SVC_DTYPE),
+        counts[8], entries[8 entry_cap] (uint8, _lib.SVC_ENTRY_DTYPE)) of
+        device tensors (or fills `out`); entries at and past counts[0] are not
+        written, nor is anything past the capacity."""
+        import torch
+        entry_cap = int(entry_cap)
+        if out is None:
+            dev = offsets.device
+            out = self._device_outputs(offsets.numel(), dev)
+            out["entries"] = torch.empty(entry_cap * _lib.SVC_ENTRY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = _lib.Svcs(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
+                      out["entries"].data_ptr() if entry_cap else None, entry_cap)
+        _lib.check(_lib.lib().gpk_svc_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                            ctypes.byref(o), _lib.stream_ptr(stream)))
+        return out
+
+    def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.SVC_ALL,
+                   stream=None):
+        """decode with a capacity that holds every message: a first call with
+        entry_cap, and, when counts reports an overflow, a second one with
+        exactly the size it needs. With the default capacity of 0 the first
+        call only sizes. Synchronizes on the counts."""
+        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds, stream=stream)
+        counts = out["counts"].cpu().numpy().view("u4")
+        if int(counts[3]):
+            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, self.needed(counts), kinds,
+                              stream=stream)
+        return out
+
+    @classmethod
+    def decode_host(cls, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.SVC_ALL, fill=0):
+        """The same over numpy arrays on the calling thread
+        (gpk_svc_batch_host); `fill` is the byte the outputs start with."""
+        entry_cap = int(entry_cap)
+        out, b, r, _keep = cls._host_arguments(
+            data, offsets, caplens, records, layouts, fill, (("entries", lambda n: entry_cap, _lib.SVC_ENTRY_DTYPE),))
+        o = _lib.Svcs(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
+                      out["entries"].ctypes.data if entry_cap else None, entry_cap)
+        _lib.check(_lib.lib().gpk_svc_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
+                                                 ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.SVC_ALL):
+        """decode_host with the retry of decode_all."""
+        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, entry_cap, kinds)
+        if int(out["counts"][3]):
+            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, cls.needed(out["counts"]), kinds)
+        return out
+
+
 class TLSDecoder(_PostPass):
     """gpk_tls_batch (include/gpk_tls.h): the TLS messages at the end of a
     decoded device batch. Owns the workspace of the scans for up to

@@ -620,7 +620,7 @@ class DecodingLayerParser:
         self._decoders = {k: d for k, d in inst.items()
                           if not getattr(d, "tunnel_kind", 0) and not getattr(d, "control_kind", 0)
                           and not getattr(d, "dns_kind", 0) and not getattr(d, "tls_kind", 0)
-                          and not getattr(d, "ndp_kind", 0)}  # kind -> instance
+                          and not getattr(d, "ndp_kind", 0) and not getattr(d, "svc_kind", 0)}  # kind -> instance
         # layers.GRE / VXLAN / Geneve: decoded by peeling tunnel levels (gpk_tunnel_batch), by GPK_TUN_* kind
         self._tunnels = {d.tunnel_kind: d for d in inst.values() if getattr(d, "tunnel_kind", 0)}
         # layers.ICMPv4 / ICMPv6 / ICMPv6Echo / ARP: decoded after the six-layer decode (gpk_control_batch), by GPK_CTL_* kind
@@ -631,6 +631,8 @@ class DecodingLayerParser:
         self._dns = next((d for d in inst.values() if getattr(d, "dns_kind", 0)), None)
         # layers.TLS: decoded after the DNS pass (gpk_tls_batch)
         self._tls = next((d for d in inst.values() if getattr(d, "tls_kind", 0)), None)
+        # layers.DHCPv4 / DHCPv6 / NTP: decoded after the TLS pass (gpk_svc_batch), by GPK_SVC_* kind
+        self._svcs = {d.svc_kind: d for d in inst.values() if getattr(d, "svc_kind", 0)}
         self._cfg = None
 
     def AddDecodingLayer(self, d):
@@ -667,8 +669,10 @@ class DecodingLayerParser:
         return self._ctx or _default_ctx()
 
     def _post_passes(self):
-        """Whether the parser holds a tunnel, control, NDP / MLD, DNS or TLS layer: DecodeBatch returns a TunnelBatchResult."""
-        return bool(self._tunnels or self._controls or self._ndps or self._dns is not None or self._tls is not None)
+        """Whether the parser holds a tunnel, control, NDP / MLD, DNS, TLS or UDP service layer: DecodeBatch returns a
+        TunnelBatchResult."""
+        return bool(self._tunnels or self._controls or self._ndps or self._dns is not None or self._tls is not None
+                    or self._svcs)
 
     def DecodeLayers(self, data, decoded):
         """Decode one packet on the GPU; fills the registered layers and the
@@ -713,10 +717,16 @@ class DecodingLayerParser:
         A parser that holds layers.TLS does too: after the DNS pass the TLS
         pass (gpk_tls_batch) decodes the records, and the ClientHello with its
         server name, of every packet whose decode stopped in front of
-        LayerTypeTLS, on every tunnel level (TLS(i), SNIs())."""
+        LayerTypeTLS, on every tunnel level (TLS(i), SNIs()).
+
+        A parser that holds layers.DHCPv4, DHCPv6 or NTP does so as well:
+        after the TLS pass the service pass (gpk_svc_batch) decodes the
+        message of every packet whose decode stopped in front of one of them,
+        on every tunnel level (Service(i)). The passes' candidates are
+        disjoint."""
         if self._post_passes():
             if fields:
-                raise ValueError("fields=True is not available for a parser with tunnel, control, NDP, DNS or TLS layers")
+                raise ValueError("fields=True is not available for a parser with tunnel, control, NDP, DNS, TLS or service layers")
             return TunnelBatchResult(self, batch, outputs, gre_checksum, checksum=checksum)
         cfg = self._config(outputs)
         if fields:
@@ -998,11 +1008,13 @@ class TunnelPart:
     (host arrays: records, rrs and names cut to what was written), or None
     when the parser holds no layers.DNS; tls: gpk_tls_batch's outputs for it
     (host arrays: records, recs, hellos and snis cut to what was written), or
-    None when the parser holds no layers.TLS."""
+    None when the parser holds no layers.TLS; svc: gpk_svc_batch's outputs for
+    it (host arrays: records and entries cut to what was written), or None
+    when the parser holds none of DHCPv4, DHCPv6 and NTP."""
 
-    def __init__(self, first, index, batch, result, peel, control=None, dns=None, tls=None, ndp=None):
+    def __init__(self, first, index, batch, result, peel, control=None, dns=None, tls=None, ndp=None, svc=None):
         self.first, self.index, self.batch, self.result, self.peel = first, index, batch, result, peel
-        self.control, self.dns, self.tls, self.ndp = control, dns, tls, ndp
+        self.control, self.dns, self.tls, self.ndp, self.svc = control, dns, tls, ndp, svc
 
 
 class TunnelBatchResult:
@@ -1026,6 +1038,9 @@ class TunnelBatchResult:
         self._ndp_kinds = _lib.NDP_ICMP6 if parser._ndps and _lib.CTL_ICMP6 in parser._controls else 0
         for k in parser._ndps:
             self._ndp_kinds |= k
+        self._svc_kinds = 0  # the service pass's kinds: which of DHCPv4, DHCPv6 and NTP the parser holds
+        for k in parser._svcs:
+            self._svc_kinds |= k
         run = self._run_device if device else self._run_host
         run(outputs, kinds, gre_checksum)
 
@@ -1033,7 +1048,7 @@ class TunnelBatchResult:
         import copy
         p = copy.copy(self.parser)  # shares the layer instances: the innermost decode fills them last
         p.first, p._tunnels, p._controls, p._dns, p._tls, p._cfg = LayerType(first), {}, {}, None, None, None
-        p._ndps = {}
+        p._ndps, p._svcs = {}, {}
         return p
 
     @staticmethod
@@ -1043,12 +1058,13 @@ class TunnelBatchResult:
                     counts=np.zeros(8, np.uint32), index=np.zeros(0, np.uint32), in_offsets=np.zeros(0, np.uint64),
                     in_caplens=np.zeros(0, np.uint32), tunnels=np.zeros(0, _lib.TUNNEL_DTYPE))
 
-    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None, tls=None, ndp=None):
+    def _add_part(self, level, first, index, offsets, caplens, r, peel, control=None, dns=None, tls=None, ndp=None,
+                  svc=None):
         if len(self.levels) <= level:
             self.levels.append([])
         p = self._clone(first)
         part = TunnelPart(LayerType(first), index, PacketBatch(self.batch.data, offsets, caplens),
-                          BatchResult(p, None, r), peel, control, dns, tls, ndp)
+                          BatchResult(p, None, r), peel, control, dns, tls, ndp, svc)
         part.result.batch = part.batch
         self.levels[level].append(part)
         for pos, g in enumerate(index):
@@ -1074,7 +1090,7 @@ class TunnelBatchResult:
         return work + [(lt, np.array(js)) for lt, js in sorted(rest.items())]
 
     def _run_host(self, outputs, kinds, gre_checksum):
-        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, TLSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, ServiceDecoder, TLSDecoder
         b = self.batch
         work = [(int(self.parser.first), np.arange(len(b)), b.offsets, b.caplens)]
         level = 0
@@ -1095,14 +1111,16 @@ class TunnelBatchResult:
                     if self.parser._dns is not None else None
                 tls = TLSDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg) \
                     if self.parser._tls is not None else None
-                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns, tls, ndp)
+                svc = ServiceDecoder.decode_host_all(b.data, offs, caps, r["records"], r["layouts"], cfg,
+                                                     kinds=self._svc_kinds) if self._svc_kinds else None
+                part = self._add_part(level, first, index, offs, caps, r, pl, ctl, dns, tls, ndp, svc)
                 for lt, js in self._next_work(part, level):
                     nxt.append((lt, index[pl["index"][js]], pl["in_offsets"][js], pl["in_caplens"][js]))
             work, level = nxt, level + 1
 
     def _run_device(self, outputs, kinds, gre_checksum):
         import torch
-        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, TLSDecoder
+        from .flows import ControlDecoder, Detunneler, DNSDecoder, NDPDecoder, ServiceDecoder, TLSDecoder
         b = self.batch
         ctx = self.parser.ctx()
         dev = torch.device("cuda", ctx.device)
@@ -1114,6 +1132,7 @@ class TunnelBatchResult:
         ndd = NDPDecoder(max(len(b), 1), ctx.device) if self._ndp_kinds else None
         dnd = DNSDecoder(max(len(b), 1), ctx.device) if self.parser._dns is not None else None
         tld = TLSDecoder(max(len(b), 1), ctx.device) if self.parser._tls is not None else None
+        svd = ServiceDecoder(max(len(b), 1), ctx.device) if self._svc_kinds else None
         try:
             work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
                      torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
@@ -1135,6 +1154,7 @@ class TunnelBatchResult:
                     nout = ndd.decode_all(ctx, data, offs, caps, rec, lay, cfg, kinds=self._ndp_kinds) if ndd else None
                     dout = dnd.decode_all(ctx, data, offs, caps, rec, lay, cfg) if dnd else None
                     tout = tld.decode_all(ctx, data, offs, caps, rec, lay, cfg) if tld else None
+                    sout = svd.decode_all(ctx, data, offs, caps, rec, lay, cfg, kinds=self._svc_kinds) if svd else None
                     torch.cuda.synchronize(dev)
                     r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
                              err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
@@ -1184,9 +1204,19 @@ class TunnelBatchResult:
                                    hellos=tout["hellos"][:need_hello * _lib.TLS_HELLO_DTYPE.itemsize].cpu().numpy().view(
                                        _lib.TLS_HELLO_DTYPE),
                                    snis=tout["snis"][:need_sni].cpu().numpy())
+                    svc = None
+                    if sout is not None:
+                        sc = sout["counts"].cpu().numpy().view(np.uint32)
+                        svc = dict(verdict=sout["verdict"].cpu().numpy(),
+                                   class_start=sout["class_start"].cpu().numpy().view(np.uint32), counts=sc,
+                                   index=sout["index"][:int(sc[0])].cpu().numpy().view(np.uint32),
+                                   records=sout["records"][:int(sc[0]) * _lib.SVC_DTYPE.itemsize].cpu().numpy().view(
+                                       _lib.SVC_DTYPE),
+                                   entries=sout["entries"][:ServiceDecoder.needed(sc) * _lib.SVC_ENTRY_DTYPE.itemsize]
+                                   .cpu().numpy().view(_lib.SVC_ENTRY_DTYPE))
                     if out is None:
                         self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls, ndp)
+                                       caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls, ndp, svc)
                         continue
                     m = int(out["counts"][0].item())
                     pl = dict(verdict=out["verdict"].cpu().numpy(),
@@ -1198,7 +1228,7 @@ class TunnelBatchResult:
                               tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
                                   _lib.TUNNEL_DTYPE))
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
-                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls, ndp)
+                                          caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls, ndp, svc)
                     for lt, js in self._next_work(part, level):
                         if len(js) and int(js[-1]) - int(js[0]) + 1 == len(js):  # a class: a zero-copy slice of the outputs
                             io, ic = out["in_offsets"][int(js[0]):int(js[-1]) + 1], out["in_caplens"][int(js[0]):int(js[-1]) + 1]
@@ -1208,7 +1238,7 @@ class TunnelBatchResult:
                         nxt.append((lt, index[pl["index"][js]], io, ic))
                 work, level = nxt, level + 1
         finally:
-            for h in (det, ctd, ndd, dnd, tld):
+            for h in (det, ctd, ndd, dnd, tld, svd):
                 if h is not None:
                     h.close()
 
@@ -1251,6 +1281,28 @@ class TunnelBatchResult:
         if t is None:
             return None
         return t, self._ndp_entries(part, t)
+
+    def _svc(self, part, pos):
+        """The gpk_svc record of a part's packet, or None: not a candidate."""
+        if part.svc is None:
+            return None
+        v = int(part.svc["verdict"][pos])
+        return part.svc["records"][v] if v >= 0 else None
+
+    @staticmethod
+    def _svc_entries(part, t):
+        e0 = int(t["entry0"])
+        return part.svc["entries"][e0:e0 + int(t["nentries"])]
+
+    def Service(self, i):
+        """(the gpk_svc record (SVC_DTYPE), its gpk_svc_entry descriptors
+        (SVC_ENTRY_DTYPE), one per DHCP option) of packet i, or None: not a
+        candidate. A failed message has no entries."""
+        part, pos = self._chain[i][-1]
+        t = self._svc(part, pos)
+        if t is None:
+            return None
+        return t, self._svc_entries(part, t)
 
     def _dns(self, part, pos):
         """The gpk_dns record of a part's packet, or None: not a candidate."""
@@ -1333,6 +1385,9 @@ class TunnelBatchResult:
             s = self._tls(part, pos)
             if s is not None and not int(s["err"]):
                 out.append(LayerType(_lib.LT_TLS))
+            u = self._svc(part, pos)
+            if u is not None and not int(u["err"]):
+                out.append(LayerType(int(u["layer_type"])))
         return out
 
     def Truncated(self, i):
@@ -1343,7 +1398,9 @@ class TunnelBatchResult:
             d = self._dns(part, pos)
             s = self._tls(part, pos)
             m = self._ndp(part, pos)
+            u = self._svc(part, pos)
             tr = tr or (m is not None and bool(int(m["status"]) & _lib.NDP_ST_TRUNCATED))
+            tr = tr or (u is not None and bool(int(u["status"]) & _lib.SVC_ST_TRUNCATED))
             tr = tr or part.result.Truncated(pos) or (t is not None and bool(int(t["status"]) & _lib.TUN_ST_TRUNCATED)) \
                 or (c is not None and bool(int(c["status"]) & _lib.CTL_ST_TRUNCATED)) \
                 or (d is not None and bool(int(d["status"]) & _lib.DNS_ST_TRUNCATED)) \
@@ -1356,6 +1413,17 @@ class TunnelBatchResult:
         part, pos = self._chain[i][-1]
         t = self._tunnel(part, pos)
         c = self._control(part, pos)
+        u = self._svc(part, pos)
+        if u is not None:  # every one of the three ends the loop: its error, or nil
+            code = int(u["err"])
+            if code:
+                buf = ctypes.create_string_buffer(256)
+                _lib.lib().gpk_svc_format_error(code, int(u["err_a0"]), int(u["err_a1"]), buf, 256)
+                msg = buf.value.decode()
+                if code == _lib.ERR_PANIC_SLICE_B and self.parser.IgnorePanic:
+                    raise GoPanic(msg[len("panic: "):])
+                return GoError(msg)
+            return None
         s = self._tls(part, pos)
         if s is not None:  # TLS has no payload: its error, or nil (tls.go:202-209)
             code = int(s["err"])
@@ -1439,6 +1507,10 @@ class TunnelBatchResult:
             s = self._tls(part, pos)
             if s is not None and not int(s["err"]):
                 p._tls._from_record(s, *self._tls_entries(part, s), part.batch.packet(pos))
+            u = self._svc(part, pos)
+            if u is not None and not int(u["err"]):
+                p._svcs[_lib.SVC_KIND_OF_TYPE[int(u["layer_type"])]]._from_record(
+                    u, self._svc_entries(part, u), part.batch.packet(pos))
         decoded[:] = self.Decoded(i)
         p.Truncated = self.Truncated(i)
         return self.Err(i)

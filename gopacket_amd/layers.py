@@ -1876,6 +1876,263 @@ NDP_LAYERS = (ICMPv6RouterSolicitation, ICMPv6RouterAdvertisement, ICMPv6Neighbo
               MLDv2MulticastListenerQueryMessage, MLDv2MulticastListenerReportMessage)
 
 
+# ---- layers/dhcpv4.go, dhcpv6.go, dhcpv6_options.go, ntp.go ----------------------
+# A DecodingLayerParser that holds DHCPv4, DHCPv6 or NTP decodes the messages on
+# the device after the TLS pass (gpk_svc_batch); the struct is filled from the
+# packet's gpk_svc record, its gpk_svc_entry descriptors and the packet's bytes
+# (_from_record). SerializeTo, the String() forms and the typed interpretation
+# of option data (DHCPv6DUID, IA_NA contents) are not built.
+LayerTypeNTP = _lt("NTP")
+LayerTypeDHCPv4 = _lt("DHCPv4")
+LayerTypeDHCPv6 = _lt("DHCPv6")
+
+
+def _named_int(name, names, unknown="Unknown"):
+    """An int subclass whose String() looks its value up in `names`."""
+    return type(name, (int,), {"String": lambda self: names.get(int(self), unknown), "__slots__": ()})
+
+
+def _export(cls, prefix, table):
+    """prefix + suffix = cls(value) for every (value, suffix, text) of table; returns {value: text}."""
+    for value, suffix, _ in table:
+        globals()[prefix + suffix] = cls(value)
+    return {value: text for value, _, text in table}
+
+
+# dhcpv4.go:18-79: DHCPOp and DHCPMsgType
+_DHCP_OP_NAMES, _DHCP_MSG_NAMES, _DHCP_OPT_NAMES, _DHCP6_MSG_NAMES, _DHCP6_OPT_NAMES = {}, {}, {}, {}, {}
+DHCPOp = _named_int("DHCPOp", _DHCP_OP_NAMES)
+DHCPMsgType = _named_int("DHCPMsgType", _DHCP_MSG_NAMES)
+DHCPOpt = _named_int("DHCPOpt", _DHCP_OPT_NAMES)          # dhcpv4.go:262-474
+DHCPv6MsgType = _named_int("DHCPv6MsgType", _DHCP6_MSG_NAMES)  # dhcpv6.go:18-72
+DHCPv6Opt = _named_int("DHCPv6Opt", _DHCP6_OPT_NAMES)      # dhcpv6_options.go:17-594
+DHCPMagic = 0x63825363
+_DHCP_OP_NAMES.update(_export(DHCPOp, "DHCPOp", [(1, "Request", "Request"), (2, "Reply", "Reply")]))
+_DHCP_MSG_NAMES.update(_export(DHCPMsgType, "DHCPMsgType", [
+    (k, n, n) for k, n in enumerate("Unspecified Discover Offer Request Decline Ack Nak Release Inform".split())]))
+_DHCP_OPT_NAMES.update(_export(DHCPOpt, "DHCPOpt", [
+    (0, "Pad", "(padding)"), (1, "SubnetMask", "SubnetMask"), (2, "TimeOffset", "TimeOffset"), (3, "Router", "Router"),
+    (4, "TimeServer", "rfc868"), (5, "NameServer", "ien116"), (6, "DNS", "DNS"), (7, "LogServer", "mitLCS"),
+    (8, "CookieServer", "CookieServer"), (9, "LPRServer", "LPRServer"), (10, "ImpressServer", "ImpressServer"),
+    (11, "ResLocServer", "ResourceLocationServer"), (12, "Hostname", "Hostname"), (13, "BootfileSize", "BootfileSize"),
+    (14, "MeritDumpFile", "MeritDumpFile"), (15, "DomainName", "DomainName"), (16, "SwapServer", "SwapServer"),
+    (17, "RootPath", "RootPath"), (18, "ExtensionsPath", "ExtensionsPath"), (19, "IPForwarding", "IPForwarding"),
+    (20, "SourceRouting", "SourceRouting"), (21, "PolicyFilter", "PolicyFilter"), (22, "DatagramMTU", "DatagramMTU"),
+    (23, "DefaultTTL", "DefaultTTL"), (24, "PathMTUAgingTimeout", "PathMTUAgingTimeout"),
+    (25, "PathPlateuTableOption", "PathPlateuTableOption"), (26, "InterfaceMTU", "InterfaceMTU"),
+    (27, "AllSubsLocal", "AllSubsLocal"), (28, "BroadcastAddr", "BroadcastAddress"), (29, "MaskDiscovery", "MaskDiscovery"),
+    (30, "MaskSupplier", "MaskSupplier"), (31, "RouterDiscovery", "RouterDiscovery"), (32, "SolicitAddr", "SolicitAddr"),
+    (33, "StaticRoute", "StaticRoute"), (34, "ARPTrailers", "ARPTrailers"), (35, "ARPTimeout", "ARPTimeout"),
+    (36, "EthernetEncap", "EthernetEncap"), (37, "TCPTTL", "TCPTTL"), (38, "TCPKeepAliveInt", "TCPKeepAliveInt"),
+    (39, "TCPKeepAliveGarbage", "TCPKeepAliveGarbage"), (40, "NISDomain", "NISDomain"), (41, "NISServers", "NISServers"),
+    (42, "NTPServers", "NTPServers"), (43, "VendorOption", "VendorOption"), (44, "NetBIOSTCPNS", "NetBIOSOverTCPNS"),
+    (45, "NetBIOSTCPDDS", "NetBiosOverTCPDDS"), (46, "NETBIOSTCPNodeType", "NetBIOSOverTCPNodeType"),
+    (47, "NetBIOSTCPScope", "NetBIOSOverTCPScope"), (48, "XFontServer", "XFontServer"),
+    (49, "XDisplayManager", "XDisplayManager"), (50, "RequestIP", "RequestIP"), (51, "LeaseTime", "LeaseTime"),
+    (52, "ExtOptions", "ExtOpts"), (53, "MessageType", "MessageType"), (54, "ServerID", "ServerID"),
+    (55, "ParamsRequest", "ParamsRequest"), (56, "Message", "Message"), (57, "MaxMessageSize", "MaxDHCPSize"),
+    (58, "T1", "Timer1"), (59, "T2", "Timer2"), (60, "ClassID", "ClassID"), (61, "ClientID", "ClientID"),
+    (119, "DomainSearch", "DomainSearch"), (120, "SIPServers", "SipServers"),
+    (121, "ClasslessStaticRoute", "ClasslessStaticRoute"), (161, "MUDURLV4", "ManufacturerUsageDescriptionURL"),
+    (255, "End", "(end)")]))
+_DHCP6_MSG_NAMES.update(_export(DHCPv6MsgType, "DHCPv6MsgType", [
+    (k, n, n) for k, n in enumerate(("Unspecified Solicit Advertise Request Confirm Renew Rebind Reply Release Decline "
+                                     "Reconfigure InformationRequest RelayForward RelayReply").split())]))
+_DHCP6_OPT_NAMES.update(_export(DHCPv6Opt, "DHCPv6Opt", [
+    (1, "ClientID", "ClientID"), (2, "ServerID", "ServerID"), (3, "IANA", "IA_NA"), (4, "IATA", "IA_TA"),
+    (5, "IAAddr", "IAAddr"), (6, "Oro", "Oro"), (7, "Preference", "Preference"), (8, "ElapsedTime", "ElapsedTime"),
+    (9, "RelayMessage", "RelayMessage"), (11, "Auth", "Auth"), (12, "Unicast", "Unicast"), (13, "StatusCode", "StatusCode"),
+    (14, "RapidCommit", "RapidCommit"), (15, "UserClass", "UserClass"), (16, "VendorClass", "VendorClass"),
+    (17, "VendorOpts", "VendorOpts"), (18, "InterfaceID", "InterfaceID"), (19, "ReconfigureMessage", "ReconfigureMessage"),
+    (20, "ReconfigureAccept", "ReconfigureAccept"), (21, "SIPServersDomainList", "SIPServersDomainList"),
+    (22, "SIPServersAddressList", "SIPServersAddressList"), (23, "DNSServers", "DNSRecursiveNameServer"),
+    (24, "DomainList", "DomainSearchList"), (25, "IAPD", "IdentityAssociationPrefixDelegation"),
+    (26, "IAPrefix", "IAPDPrefix"), (27, "NISServers", "NISServers"), (28, "NISPServers", "NISv2Servers"),
+    (29, "NISDomainName", "NISDomainName"), (30, "NISPDomainName", "NISv2DomainName"), (31, "SNTPServers", "SNTPServers"),
+    (32, "InformationRefreshTime", "InformationRefreshTime"),
+    (33, "BCMCSServerDomainNameList", "BCMCSControlServersDomainNameList"),
+    (34, "BCMCSServerAddressList", "BCMCSControlServersAddressList"), (36, "GeoconfCivic", "CivicAddress"),
+    (37, "RemoteID", "RelayAgentRemoteID"), (38, "SubscriberID", "RelayAgentSubscriberID"), (39, "ClientFQDN", "ClientFQDN"),
+    (40, "PanaAgent", "PANAAuthenticationAgent"), (41, "NewPOSIXTimezone", "NewPOSIXTimezone"),
+    (42, "NewTZDBTimezone", "NewTZDBTimezone"), (43, "EchoRequestOption", "EchoRequest"), (44, "LQQuery", "LeasequeryQuery"),
+    (45, "CLTTime", "LeasequeryClientLastTransactionTime"), (46, "ClientData", "LeasequeryClientData"),
+    (47, "LQRelayData", "LeasequeryRelayData"), (48, "LQClientLink", "LeasequeryClientLink"),
+    (49, "MIP6HNIDF", "MIPv6HomeNetworkIDFQDN"), (50, "MIP6VDINF", "MIPv6VisitedHomeNetworkInformation"),
+    (51, "V6LOST", "LoST Server"), (52, "CAPWAPACV6", "CAPWAPAccessControllerV6"), (53, "RelayID", "LeasequeryRelayID"),
+    (54, "IPv6AddressMoS", "MoSIPv6Address"), (55, "IPv6FQDNMoS", "MoSDomainNameList"), (56, "NTPServer", "NTPServer"),
+    (57, "V6AccessDomain", "AccessNetworkDomainName"), (58, "SIPUACSList", "SIPUserAgentConfigurationServiceDomains"),
+    (59, "BootFileURL", "BootFileURL"), (60, "BootFileParam", "BootFileParameters"),
+    (61, "ClientArchType", "ClientSystemArchitectureType"), (62, "NII", "ClientNetworkInterfaceIdentifier"),
+    (63, "Geolocation", "Geolocation"), (64, "AFTRName", "AFTRName"), (65, "ERPLocalDomainName", "AFTRName"),
+    (66, "RSOO", "RSOOption"), (67, "PDExclude", "PrefixExclude"), (68, "VSS", "VirtualSubnetSelection"),
+    (69, "MIP6IDINF", "MIPv6IdentifiedHomeNetworkInformation"), (70, "MIP6UDINF", "MIPv6UnrestrictedHomeNetworkInformation"),
+    (71, "MIP6HNP", "MIPv6HomeNetworkPrefix"), (72, "MIP6HAA", "MIPv6HomeAgentAddress"), (73, "MIP6HAF", "MIPv6HomeAgentFQDN"),
+    (74, "RDNSSSelection", "RDNSSSelection"), (75, "KRBPrincipalName", "KerberosPrincipalName"),
+    (76, "KRBRealmName", "KerberosRealmName"), (77, "KRBKDC", "KerberosKDC"),
+    (79, "ClientLinkLayerAddress", "ClientLinkLayerAddress"), (80, "LinkAddress", "LinkAddress"), (81, "RADIUS", "RADIUS"),
+    (82, "SolMaxRt", "SolMaxRt"), (83, "InfMaxRt", "InfMaxRt"), (84, "AddrSel", "AddressSelection"),
+    (85, "AddrSelTable", "AddressSelectionTable"), (86, "V6PCPServer", "PCPServer"), (87, "DHCPv4Message", "DHCPv4Message"),
+    (88, "DHCPv4OverDHCPv6Server", "DHCP4o6ServerAddress"), (89, "S46Rule", "S46Rule"), (90, "S46BR", "S46BR"),
+    (91, "S46DMR", "S46DMR"), (92, "S46V4V4Bind", "S46IPv4IPv6AddressBinding"), (93, "S46PortParameters", "S46PortParameters"),
+    (94, "S46ContMAPE", "S46MAPEContainer"), (95, "S46ContMAPT", "S46MAPTContainer"),
+    (96, "S46ContLW", "S46Lightweight4Over6Container"), (97, "4RD", "4RD"), (98, "4RDMapRule", "4RDMapRule"),
+    (99, "4RDNonMapRule", "4RDNonMapRule"), (100, "LQBaseTime", "LQBaseTime"), (101, "LQStartTime", "LQStartTime"),
+    (102, "LQEndTime", "LQEndTime"), (103, "CaptivePortal", "CaptivePortal"), (104, "MPLParameters", "MPLParameterConfiguration"),
+    (105, "ANIATT", "ANIAccessTechnologyType"), (106, "ANINetworkName", "ANINetworkName"), (107, "ANIAPName", "ANIAccessPointName"),
+    (108, "ANIAPBSSID", "ANIAccessPointBSSID"), (109, "ANIOperatorID", "ANIOperatorIdentifier"),
+    (110, "ANIOperatorRealm", "ANIOperatorRealm"), (111, "S46Priority", "S64Priority"),
+    (112, "MUDURLV6", "ManufacturerUsageDescriptionURL"), (113, "V6Prefix64", "V6Prefix64"),
+    (135, "RelayPort", "RelayPort"), (136, "V6ZeroTouchRedirect", "ZeroTouch"), (143, "IPV6AddressANDSF", "ANDSFIPv6Address")]))
+_DHCP6_OPT_NAMES.update(_export(DHCPv6Opt, "DHCPv6OptF", [  # the failover options of RFC 8156
+    (114 + k, s, "Failover" + n) for k, (s, n) in enumerate([
+        ("BindingStatus", "BindingStatus"), ("ConnectFlags", "ConnectFlags"), ("DNSRemovalInfo", "DNSRemovalInfo"),
+        ("DNSHostName", "DNSHostName"), ("DNSZoneName", "DNSZoneName"), ("DNSFlags", "DNSFlags"),
+        ("ExpirationTime", "ExpirationTime"), ("MaxUnacknowledgedBNDUPD", "MaxUnacknowledgedBNDUPDMessages"),
+        ("MCLT", "MaximumClientLeadTime"), ("PartnerLifetime", "PartnerLifetime"),
+        ("PartnerLifetimeSent", "PartnerLifetimeSent"), ("PartnerDownTime", "PartnerDownTime"),
+        ("PartnerRawCltTime", "PartnerRawClientLeadTime"), ("ProtocolVersion", "ProtocolVersion"),
+        ("KeepaliveTime", "KeepaliveTime"), ("ReconfigureData", "ReconfigureData"), ("RelationshipName", "RelationshipName"),
+        ("ServerFlags", "ServerFlags"), ("ServerState", "ServerState"), ("StartTimeOfState", "StartTimeOfState"),
+        ("StateExpirationTime", "StateExpirationTime")])]))
+
+
+class DHCPOption:
+    """dhcpv4.go:478-482. A Pad has Length 0 and no Data."""
+
+    def __init__(self, Type=0, Length=0, Data=b""):
+        self.Type, self.Length, self.Data = DHCPOpt(Type), int(Length), bytes(Data)
+
+    def __eq__(self, o):
+        return isinstance(o, DHCPOption) and (int(self.Type), self.Length, self.Data) == (int(o.Type), o.Length, o.Data)
+
+    def __repr__(self):
+        return "DHCPOption(%s, %d, %r)" % (self.Type.String(), self.Length, self.Data)
+
+
+class DHCPOptions(list):
+    """dhcpv4.go:476"""
+
+
+class DHCPv6Option:
+    """dhcpv6_options.go:559-563"""
+
+    def __init__(self, Code=0, Length=0, Data=b""):
+        self.Code, self.Length, self.Data = DHCPv6Opt(Code), int(Length), bytes(Data)
+
+    def __eq__(self, o):
+        return isinstance(o, DHCPv6Option) and (int(self.Code), self.Length, self.Data) == (int(o.Code), o.Length, o.Data)
+
+    def __repr__(self):
+        return "DHCPv6Option(%s, %d, %r)" % (self.Code.String(), self.Length, self.Data)
+
+
+class DHCPv6Options(list):
+    """dhcpv6_options.go:557"""
+
+
+class _SvcLayer(BaseLayer):
+    _lt = None
+    _next = LayerTypePayload
+
+    def DecodeFromBytes(self, data, df):
+        raise NotImplementedError("DHCPv4, DHCPv6 and NTP decode through a DecodingLayerParser (DecodeLayers / DecodeBatch)")
+
+    def LayerType(self):
+        return self._lt
+
+    def CanDecode(self):
+        return LayerClass([self._lt])
+
+    def NextLayerType(self):
+        return self._next
+
+    def _base(self, t, pkt):
+        h = int(t["hdr_off"])
+        self.Contents = pkt[h:h + int(t["contents_len"])]
+        self.Payload = b""
+
+
+class DHCPv4(_SvcLayer):
+    """dhcpv4.go:84-101, 126-184"""
+    kind = 500 + 0
+    svc_kind = _lib.SVC_DHCP4
+    _lt = LayerTypeDHCPv4
+
+    def __init__(self):
+        self.Operation, self.HardwareType, self.HardwareLen, self.RelayHops = DHCPOp(0), 0, 0, 0
+        self.Xid = self.Secs = self.Flags = 0
+        self.ClientIP = self.YourClientIP = self.NextServerIP = self.RelayAgentIP = b""
+        self.ClientHWAddr = self.ServerName = self.File = b""
+        self.Options = DHCPOptions()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        h, b, v = int(t["hdr_off"]), t["b"], t["v"]
+        self.Operation, self.HardwareType, self.HardwareLen, self.RelayHops = DHCPOp(int(b[0])), int(b[1]), int(b[2]), int(b[3])
+        self.Xid, self.Secs, self.Flags = int(v[0]), int(v[1]) & 0xffff, int(v[1]) >> 16
+        ips = v[2:6].astype("<u4").tobytes()
+        self.ClientIP, self.YourClientIP, self.NextServerIP, self.RelayAgentIP = (ips[4 * k:4 * k + 4] for k in range(4))
+        self.ClientHWAddr = pkt[h + 28:h + 28 + self.HardwareLen]
+        self.ServerName, self.File = pkt[h + 44:h + 108], pkt[h + 108:h + 236]
+        self.Options = DHCPOptions(
+            DHCPOption(int(e["code"]), int(e["length"]), pkt[int(e["off"]):int(e["off"]) + int(e["length"])]) for e in entries)
+
+
+class DHCPv6(_SvcLayer):
+    """dhcpv6.go:74-124"""
+    kind = 500 + 1
+    svc_kind = _lib.SVC_DHCP6
+    _lt = LayerTypeDHCPv6
+
+    def __init__(self):
+        self.MsgType, self.HopCount = DHCPv6MsgType(0), 0
+        self.LinkAddr = self.PeerAddr = self.TransactionID = b""
+        self.Options = DHCPv6Options()
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        b, v = t["b"], t["v"]
+        self.MsgType, self.HopCount = DHCPv6MsgType(int(b[0])), int(b[1])
+        self.LinkAddr = self.PeerAddr = self.TransactionID = b""
+        if int(self.MsgType) in (12, 13):
+            self.LinkAddr, self.PeerAddr = pkt[int(v[1]):int(v[1]) + 16], pkt[int(v[2]):int(v[2]) + 16]
+        else:
+            self.TransactionID = int(v[0]).to_bytes(3, "big")
+        self.Options = DHCPv6Options(
+            DHCPv6Option(int(e["code"]), int(e["length"]), pkt[int(e["off"]):int(e["off"]) + int(e["length"])])
+            for e in entries)
+
+
+class NTP(_SvcLayer):
+    """ntp.go:166-253, 294-347. The scalar types (NTPLeapIndicator, NTPVersion,
+    NTPMode, NTPStratum, NTPLog2Seconds, NTPFixed16Seconds, NTPReferenceID,
+    NTPTimestamp) are plain ints; Poll and Precision are signed."""
+    kind = 500 + 2
+    svc_kind = _lib.SVC_NTP
+    _lt = LayerTypeNTP
+    _next = LayerType(0)
+
+    def __init__(self):
+        self.LeapIndicator = self.Version = self.Mode = self.Stratum = self.Poll = self.Precision = 0
+        self.RootDelay = self.RootDispersion = self.ReferenceID = 0
+        self.ReferenceTimestamp = self.OriginTimestamp = self.ReceiveTimestamp = self.TransmitTimestamp = 0
+        self.ExtensionBytes = b""
+
+    def _from_record(self, t, entries, pkt):
+        self._base(t, pkt)
+        h, b, v = int(t["hdr_off"]), t["b"], t["v"]
+        self.LeapIndicator, self.Version, self.Mode, self.Stratum = (int(x) for x in b)
+        s8 = lambda x: x - 256 if x > 127 else x  # noqa: E731
+        self.Poll, self.Precision = s8(int(v[0]) & 0xff), s8(int(v[0]) >> 8 & 0xff)
+        self.RootDelay, self.RootDispersion, self.ReferenceID = int(v[1]), int(v[2]), int(v[3])
+        (self.ReferenceTimestamp, self.OriginTimestamp, self.ReceiveTimestamp,
+         self.TransmitTimestamp) = struct.unpack(">4Q", pkt[h + 16:h + 48])  # the record does not carry them
+        self.ExtensionBytes = pkt[int(v[4]):int(v[4]) + int(v[5])]
+
+
+SVC_LAYERS = (DHCPv4, DHCPv6, NTP)
+
+
 # ---- layers/dns.go ------------------------------------------------------------------
 # A DecodingLayerParser that holds layers.DNS decodes the messages on the device
 # after the six-layer decode and the control pass (gpk_dns_batch); the struct is
