@@ -905,11 +905,20 @@ class Serializer(_Handle):
         return res
 
 
+def _per_packet(n):
+    return n
+
+
+def _per_entry(n):  # of the compact list: room for n, counts[0] of them written
+    return n
+
+
 class _PostPass(_Handle):
     """A pass over a decoded device batch that writes a compact list ordered by
     class (csrc/gpk_postpass.h). A subclass names its entry points, its _lib
     output struct, the flag that asks for the sums and OUTPUTS: (key, count for
-    n packets, numpy dtype) of every array of that struct, in its order."""
+    n packets, numpy dtype) of every array of that struct, in its order; the
+    count of an array with one element per entry of the list is _per_entry."""
 
     _batch = _batch_host = _set_threshold = _Out = _FLAG = None
     OUTPUTS = ()
@@ -971,6 +980,100 @@ class _PostPass(_Handle):
                                                         cls._FLAG if sums else 0, ctypes.byref(o)))
         return out
 
+    @classmethod
+    def to_host(cls, out):
+        """A device result as numpy arrays of the OUTPUTS dtypes, cut to what
+        the call wrote: the per-entry arrays to counts[0] entries, the others
+        whole. Synchronizes."""
+        import numpy as np
+        m = int(out["counts"][0].item())
+        host = {}
+        for key, count, dt in cls.OUTPUTS:
+            dt = np.dtype(dt)
+            t = out[key][:m * (dt.itemsize if dt.fields else 1)] if count is _per_entry else out[key]
+            host[key] = t.cpu().numpy().view(dt)
+        return host
+
+
+class _ArenaPass(_PostPass):
+    """A _PostPass whose result has a variable length (csrc/gpk_arena.h): the
+    entries name ranges of arenas of the caller's capacities. A subclass adds
+    ARENAS: (key, numpy dtype, the first of the two counts words that hold its
+    need) of every arena, in the order of the output struct, which ends with
+    their pointers and then their capacities. `batch` is (data, offsets,
+    caplens, records, layouts, parser), `caps` a capacity per arena, `kinds`
+    None where the entry points take none."""
+
+    ARENAS = ()
+
+    @classmethod
+    def _needs(cls, counts):
+        c = [int(x) & 0xffffffff for x in counts]
+        return tuple(c[w] | c[w + 1] << 32 for _, _, w in cls.ARENAS)
+
+    @classmethod
+    def needed(cls, counts):
+        """What the batch needs of each arena, from counts (uint32): a tuple in
+        the order of the capacities, or the one number where there is one."""
+        needs = cls._needs(counts)
+        return needs if len(needs) > 1 else needs[0]
+
+    @classmethod
+    def _out_struct(cls, out, caps, ptr):
+        return cls._Out(*[ptr(out[key]) for key, _, _ in cls.OUTPUTS],
+                        *[ptr(out[key]) if cap else None for (key, _, _), cap in zip(cls.ARENAS, caps)], *caps)
+
+    def _decode(self, ctx, batch, caps, kinds, out, stream):
+        import numpy as np
+        import torch
+        data, offsets, caplens, records, layouts, parser = batch
+        caps = [int(cap) for cap in caps]
+        if out is None:
+            dev = offsets.device
+            out = self._device_outputs(offsets.numel(), dev)
+            for (key, dt, _), cap in zip(self.ARENAS, caps):
+                out[key] = torch.empty(cap * np.dtype(dt).itemsize, dtype=torch.uint8, device=dev)
+        b = _lib.Batch.of(data, offsets, caplens)
+        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
+        o = self._out_struct(out, caps, lambda t: t.data_ptr())
+        _lib.check(getattr(_lib.lib(), self._batch)(
+            self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), *(() if kinds is None else (int(kinds),)),
+            ctypes.byref(o), _lib.stream_ptr(stream)))
+        return out
+
+    def _decode_all(self, ctx, batch, caps, kinds, stream):
+        out = self._decode(ctx, batch, caps, kinds, None, stream)
+        counts = out["counts"].cpu().numpy().view("u4")
+        if int(counts[3]):
+            out = self._decode(ctx, batch, self._needs(counts), kinds, None, stream)
+        return out
+
+    @classmethod
+    def _decode_host(cls, batch, caps, kinds, fill=0):
+        caps = [int(cap) for cap in caps]
+        out, b, r, _keep = cls._host_arguments(
+            *batch[:5], fill, [(key, lambda n, cap=cap: cap, dt) for (key, dt, _), cap in zip(cls.ARENAS, caps)])
+        o = cls._out_struct(out, caps, lambda a: a.ctypes.data)
+        _lib.check(getattr(_lib.lib(), cls._batch_host)(
+            batch[5].h, ctypes.byref(b), ctypes.byref(r), *(() if kinds is None else (int(kinds),)), ctypes.byref(o)))
+        return out
+
+    @classmethod
+    def _decode_host_all(cls, batch, caps, kinds):
+        out = cls._decode_host(batch, caps, kinds)
+        if int(out["counts"][3]):
+            out = cls._decode_host(batch, cls._needs(out["counts"]), kinds)
+        return out
+
+    @classmethod
+    def to_host(cls, out):
+        """_PostPass.to_host, and each arena cut to what the batch needs."""
+        import numpy as np
+        host = super().to_host(out)
+        for (key, dt, _), need in zip(cls.ARENAS, cls._needs(host["counts"])):
+            host[key] = out[key][:need * np.dtype(dt).itemsize].cpu().numpy().view(dt)
+        return host
+
 
 class Detunneler(_PostPass):
     """gpk_tunnel_batch (include/gpk_tunnel.h): one tunnel level peeled off a
@@ -980,9 +1083,9 @@ class Detunneler(_PostPass):
     _create, _destroy = "gpk_tunneler_create", "gpk_tunneler_destroy"
     _batch, _batch_host, _set_threshold = "gpk_tunnel_batch", "gpk_tunnel_batch_host", "gpk_tunneler_set_sum_threshold"
     _Out, _FLAG = _lib.Tunnels, _lib.TUN_GRE_CSUM
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 7, "u4"), ("index", lambda n: n, "u4"),
-               ("in_offsets", lambda n: n, "u8"), ("in_caplens", lambda n: n, "u4"),
-               ("tunnels", lambda n: n, _lib.TUNNEL_DTYPE), ("counts", lambda n: 8, "u4"))
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 7, "u4"), ("index", _per_entry, "u4"),
+               ("in_offsets", _per_entry, "u8"), ("in_caplens", _per_entry, "u4"),
+               ("tunnels", _per_entry, _lib.TUNNEL_DTYPE), ("counts", lambda n: 8, "u4"))
     KEYS = tuple(k for k, _, _ in OUTPUTS)
 
     def peel(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.TUN_ALL, gre_checksum=True,
@@ -1013,8 +1116,8 @@ class ControlDecoder(_PostPass):
     _batch, _batch_host = "gpk_control_batch", "gpk_control_batch_host"
     _set_threshold = "gpk_controller_set_sum_threshold"
     _Out, _FLAG = _lib.Controls, _lib.CTL_CSUM
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 5, "u4"), ("index", lambda n: n, "u4"),
-               ("records", lambda n: n, _lib.CONTROL_DTYPE), ("counts", lambda n: 8, "u4"))
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 5, "u4"), ("index", _per_entry, "u4"),
+               ("records", _per_entry, _lib.CONTROL_DTYPE), ("counts", lambda n: 8, "u4"))
     KEYS = tuple(k for k, _, _ in OUTPUTS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, kinds=_lib.CTL_ALL, checksum=True,
@@ -1034,7 +1137,7 @@ class ControlDecoder(_PostPass):
         return cls._host(data, offsets, caplens, records, layouts, parser, kinds, checksum, fill)
 
 
-class DNSDecoder(_PostPass):
+class DNSDecoder(_ArenaPass):
     """gpk_dns_batch (include/gpk_dns.h): the DNS messages at the end of a
     decoded device batch. Owns the workspace of the scans for up to
     max_packets packets; device=None makes a host-only one (decode_host).
@@ -1046,16 +1149,11 @@ class DNSDecoder(_PostPass):
     decode_host_all size first and decode once more with exactly that."""
 
     _create, _destroy = "gpk_dns_decoder_create", "gpk_dns_decoder_destroy"
-    _Out = _lib.Dnss
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
-               ("records", lambda n: n, _lib.DNS_DTYPE), ("counts", lambda n: 8, "u4"))
-    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("rrs", "names")
-
-    @staticmethod
-    def needed(counts):
-        """(entries, name bytes) the batch needs, from counts[8] (uint32)."""
-        c = [int(x) & 0xffffffff for x in counts]
-        return c[4] | c[5] << 32, c[6] | c[7] << 32
+    _batch, _batch_host, _Out = "gpk_dns_batch", "gpk_dns_batch_host", _lib.Dnss
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 3, "u4"), ("index", _per_entry, "u4"),
+               ("records", _per_entry, _lib.DNS_DTYPE), ("counts", lambda n: 8, "u4"))
+    ARENAS = (("rrs", _lib.DNS_RR_DTYPE, 4), ("names", "u1", 6))
+    KEYS = tuple(k for k, _, _ in OUTPUTS + ARENAS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, out=None, stream=None):
         """Device tensors in: the batch (data 16-byte aligned), and the records
@@ -1064,21 +1162,7 @@ class DNSDecoder(_PostPass):
         _lib.DNS_DTYPE), counts[8], rrs[96 rr_cap] (uint8, _lib.DNS_RR_DTYPE),
         names[name_cap] (uint8)) of device tensors (or fills `out`); entries at
         and past counts[0] are not written, nor is anything past a capacity."""
-        import torch
-        rr_cap, name_cap = int(rr_cap), int(name_cap)
-        if out is None:
-            dev = offsets.device
-            out = self._device_outputs(offsets.numel(), dev)
-            out["rrs"] = torch.empty(rr_cap * _lib.DNS_RR_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            out["names"] = torch.empty(name_cap, dtype=torch.uint8, device=dev)
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Dnss(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
-                      out["rrs"].data_ptr() if rr_cap else None, out["names"].data_ptr() if name_cap else None,
-                      rr_cap, name_cap)
-        _lib.check(_lib.lib().gpk_dns_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o),
-                                            _lib.stream_ptr(stream)))
-        return out
+        return self._decode(ctx, (data, offsets, caplens, records, layouts, parser), (rr_cap, name_cap), None, out, stream)
 
     def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, rr_cap=0, name_cap=0, stream=None):
         """decode with capacities that hold every message: a first call with
@@ -1087,38 +1171,21 @@ class DNSDecoder(_PostPass):
         first call only sizes: no memory is set aside on a guess, at the price
         of a second pass whenever the batch holds a message that decodes.
         Synchronizes on the counts."""
-        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, stream=stream)
-        counts = out["counts"].cpu().numpy().view("u4")
-        if int(counts[3]):
-            rr_cap, name_cap = self.needed(counts)
-            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, stream=stream)
-        return out
+        return self._decode_all(ctx, (data, offsets, caplens, records, layouts, parser), (rr_cap, name_cap), None, stream)
 
     @classmethod
     def decode_host(cls, data, offsets, caplens, records, layouts, parser, rr_cap, name_cap, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_dns_batch_host); `fill` is the byte the outputs start with."""
-        rr_cap, name_cap = int(rr_cap), int(name_cap)
-        out, b, r, _keep = cls._host_arguments(
-            data, offsets, caplens, records, layouts, fill,
-            (("rrs", lambda n: rr_cap, _lib.DNS_RR_DTYPE), ("names", lambda n: name_cap, "u1")))
-        o = _lib.Dnss(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
-                      out["rrs"].ctypes.data if rr_cap else None, out["names"].ctypes.data if name_cap else None,
-                      rr_cap, name_cap)
-        _lib.check(_lib.lib().gpk_dns_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o)))
-        return out
+        return cls._decode_host((data, offsets, caplens, records, layouts, parser), (rr_cap, name_cap), None, fill)
 
     @classmethod
     def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, rr_cap=0, name_cap=0):
         """decode_host with the retry of decode_all."""
-        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rr_cap, name_cap)
-        if int(out["counts"][3]):
-            rr_cap, name_cap = cls.needed(out["counts"])
-            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rr_cap, name_cap)
-        return out
+        return cls._decode_host_all((data, offsets, caplens, records, layouts, parser), (rr_cap, name_cap), None)
 
 
-class NDPDecoder(_PostPass):
+class NDPDecoder(_ArenaPass):
     """gpk_ndp_batch (include/gpk_ndp.h): the NDP and MLD messages behind
     ICMPv6 at the end of a decoded device batch. Owns the workspace of the
     scans for up to max_packets packets; device=None makes a host-only one
@@ -1132,16 +1199,11 @@ class NDPDecoder(_PostPass):
     that."""
 
     _create, _destroy = "gpk_ndp_decoder_create", "gpk_ndp_decoder_destroy"
-    _Out = _lib.Ndps
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
-               ("records", lambda n: n, _lib.NDP_DTYPE), ("counts", lambda n: 8, "u4"))
-    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("entries",)
-
-    @staticmethod
-    def needed(counts):
-        """The entries the batch needs, from counts[8] (uint32)."""
-        c = [int(x) & 0xffffffff for x in counts]
-        return c[4] | c[5] << 32
+    _batch, _batch_host, _Out = "gpk_ndp_batch", "gpk_ndp_batch_host", _lib.Ndps
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 3, "u4"), ("index", _per_entry, "u4"),
+               ("records", _per_entry, _lib.NDP_DTYPE), ("counts", lambda n: 8, "u4"))
+    ARENAS = (("entries", _lib.NDP_ENTRY_DTYPE, 4),)
+    KEYS = tuple(k for k, _, _ in OUTPUTS + ARENAS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.NDP_ALL, out=None,
                stream=None):
@@ -1152,19 +1214,7 @@ class NDPDecoder(_PostPass):
         counts[8], entries[16 entry_cap] (uint8, _lib.NDP_ENTRY_DTYPE)) of
         device tensors (or fills `out`); entries at and past counts[0] are not
         written, nor is anything past the capacity."""
-        import torch
-        entry_cap = int(entry_cap)
-        if out is None:
-            dev = offsets.device
-            out = self._device_outputs(offsets.numel(), dev)
-            out["entries"] = torch.empty(entry_cap * _lib.NDP_ENTRY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Ndps(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
-                      out["entries"].data_ptr() if entry_cap else None, entry_cap)
-        _lib.check(_lib.lib().gpk_ndp_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                            ctypes.byref(o), _lib.stream_ptr(stream)))
-        return out
+        return self._decode(ctx, (data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, out, stream)
 
     def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.NDP_ALL,
                    stream=None):
@@ -1172,36 +1222,21 @@ class NDPDecoder(_PostPass):
         entry_cap, and, when counts reports an overflow, a second one with
         exactly the size it needs. With the default capacity of 0 the first
         call only sizes. Synchronizes on the counts."""
-        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds, stream=stream)
-        counts = out["counts"].cpu().numpy().view("u4")
-        if int(counts[3]):
-            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, self.needed(counts), kinds,
-                              stream=stream)
-        return out
+        return self._decode_all(ctx, (data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, stream)
 
     @classmethod
     def decode_host(cls, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.NDP_ALL, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_ndp_batch_host); `fill` is the byte the outputs start with."""
-        entry_cap = int(entry_cap)
-        out, b, r, _keep = cls._host_arguments(
-            data, offsets, caplens, records, layouts, fill, (("entries", lambda n: entry_cap, _lib.NDP_ENTRY_DTYPE),))
-        o = _lib.Ndps(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
-                      out["entries"].ctypes.data if entry_cap else None, entry_cap)
-        _lib.check(_lib.lib().gpk_ndp_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                                 ctypes.byref(o)))
-        return out
+        return cls._decode_host((data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, fill)
 
     @classmethod
     def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.NDP_ALL):
         """decode_host with the retry of decode_all."""
-        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, entry_cap, kinds)
-        if int(out["counts"][3]):
-            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, cls.needed(out["counts"]), kinds)
-        return out
+        return cls._decode_host_all((data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds)
 
 
-class ServiceDecoder(_PostPass):
+class ServiceDecoder(_ArenaPass):
     """gpk_svc_batch (include/gpk_svc.h): the DHCPv4, DHCPv6 and NTP
     messages at the end of a decoded device batch. Owns the workspace of the
     scans for up to max_packets packets; device=None makes a host-only one
@@ -1215,16 +1250,11 @@ class ServiceDecoder(_PostPass):
     that."""
 
     _create, _destroy = "gpk_svc_decoder_create", "gpk_svc_decoder_destroy"
-    _Out = _lib.Svcs
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
-               ("records", lambda n: n, _lib.SVC_DTYPE), ("counts", lambda n: 8, "u4"))
-    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("entries",)
-
-    @staticmethod
-    def needed(counts):
-        """The entries the batch needs, from counts[8] (uint32)."""
-        c = [int(x) & 0xffffffff for x in counts]
-        return c[4] | c[5] << 32
+    _batch, _batch_host, _Out = "gpk_svc_batch", "gpk_svc_batch_host", _lib.Svcs
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 3, "u4"), ("index", _per_entry, "u4"),
+               ("records", _per_entry, _lib.SVC_DTYPE), ("counts", lambda n: 8, "u4"))
+    ARENAS = (("entries", _lib.SVC_ENTRY_DTYPE, 4),)
+    KEYS = tuple(k for k, _, _ in OUTPUTS + ARENAS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.SVC_ALL, out=None,
                stream=None):
@@ -1235,19 +1265,7 @@ class ServiceDecoder(_PostPass):
         counts[8], entries[8 entry_cap] (uint8, _lib.SVC_ENTRY_DTYPE)) of
         device tensors (or fills `out`); entries at and past counts[0] are not
         written, nor is anything past the capacity."""
-        import torch
-        entry_cap = int(entry_cap)
-        if out is None:
-            dev = offsets.device
-            out = self._device_outputs(offsets.numel(), dev)
-            out["entries"] = torch.empty(entry_cap * _lib.SVC_ENTRY_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Svcs(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
-                      out["entries"].data_ptr() if entry_cap else None, entry_cap)
-        _lib.check(_lib.lib().gpk_svc_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                            ctypes.byref(o), _lib.stream_ptr(stream)))
-        return out
+        return self._decode(ctx, (data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, out, stream)
 
     def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.SVC_ALL,
                    stream=None):
@@ -1255,36 +1273,21 @@ class ServiceDecoder(_PostPass):
         entry_cap, and, when counts reports an overflow, a second one with
         exactly the size it needs. With the default capacity of 0 the first
         call only sizes. Synchronizes on the counts."""
-        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, entry_cap, kinds, stream=stream)
-        counts = out["counts"].cpu().numpy().view("u4")
-        if int(counts[3]):
-            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, self.needed(counts), kinds,
-                              stream=stream)
-        return out
+        return self._decode_all(ctx, (data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, stream)
 
     @classmethod
     def decode_host(cls, data, offsets, caplens, records, layouts, parser, entry_cap, kinds=_lib.SVC_ALL, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_svc_batch_host); `fill` is the byte the outputs start with."""
-        entry_cap = int(entry_cap)
-        out, b, r, _keep = cls._host_arguments(
-            data, offsets, caplens, records, layouts, fill, (("entries", lambda n: entry_cap, _lib.SVC_ENTRY_DTYPE),))
-        o = _lib.Svcs(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
-                      out["entries"].ctypes.data if entry_cap else None, entry_cap)
-        _lib.check(_lib.lib().gpk_svc_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), int(kinds),
-                                                 ctypes.byref(o)))
-        return out
+        return cls._decode_host((data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds, fill)
 
     @classmethod
     def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, entry_cap=0, kinds=_lib.SVC_ALL):
         """decode_host with the retry of decode_all."""
-        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, entry_cap, kinds)
-        if int(out["counts"][3]):
-            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, cls.needed(out["counts"]), kinds)
-        return out
+        return cls._decode_host_all((data, offsets, caplens, records, layouts, parser), (entry_cap,), kinds)
 
 
-class TLSDecoder(_PostPass):
+class TLSDecoder(_ArenaPass):
     """gpk_tls_batch (include/gpk_tls.h): the TLS messages at the end of a
     decoded device batch. Owns the workspace of the scans for up to
     max_packets packets; device=None makes a host-only one (decode_host).
@@ -1298,16 +1301,11 @@ class TLSDecoder(_PostPass):
     once more with exactly that."""
 
     _create, _destroy = "gpk_tls_decoder_create", "gpk_tls_decoder_destroy"
-    _Out = _lib.Tlss
-    OUTPUTS = (("verdict", lambda n: n, "i4"), ("class_start", lambda n: 3, "u4"), ("index", lambda n: n, "u4"),
-               ("records", lambda n: n, _lib.TLS_DTYPE), ("counts", lambda n: 12, "u4"))
-    KEYS = tuple(k for k, _, _ in OUTPUTS) + ("recs", "hellos", "snis")
-
-    @staticmethod
-    def needed(counts):
-        """(record entries, hello entries, server name bytes) the batch needs, from counts[12] (uint32)."""
-        c = [int(x) & 0xffffffff for x in counts]
-        return c[4] | c[5] << 32, c[6] | c[7] << 32, c[8] | c[9] << 32
+    _batch, _batch_host, _Out = "gpk_tls_batch", "gpk_tls_batch_host", _lib.Tlss
+    OUTPUTS = (("verdict", _per_packet, "i4"), ("class_start", lambda n: 3, "u4"), ("index", _per_entry, "u4"),
+               ("records", _per_entry, _lib.TLS_DTYPE), ("counts", lambda n: 12, "u4"))
+    ARENAS = (("recs", _lib.TLS_REC_DTYPE, 4), ("hellos", _lib.TLS_HELLO_DTYPE, 6), ("snis", "u1", 8))
+    KEYS = tuple(k for k, _, _ in OUTPUTS + ARENAS)
 
     def decode(self, ctx, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap, out=None,
                stream=None):
@@ -1319,22 +1317,8 @@ class TLSDecoder(_PostPass):
         _lib.TLS_HELLO_DTYPE), snis[sni_cap] (uint8)) of device tensors (or
         fills `out`); entries at and past counts[0] are not written, nor is
         anything past a capacity."""
-        import torch
-        rec_cap, hello_cap, sni_cap = int(rec_cap), int(hello_cap), int(sni_cap)
-        if out is None:
-            dev = offsets.device
-            out = self._device_outputs(offsets.numel(), dev)
-            out["recs"] = torch.empty(rec_cap * _lib.TLS_REC_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            out["hellos"] = torch.empty(hello_cap * _lib.TLS_HELLO_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-            out["snis"] = torch.empty(sni_cap, dtype=torch.uint8, device=dev)
-        b = _lib.Batch.of(data, offsets, caplens)
-        r = _lib.Results(records.data_ptr(), None, None, layouts.data_ptr())
-        o = _lib.Tlss(*[out[key].data_ptr() for key, _, _ in self.OUTPUTS],
-                      out["recs"].data_ptr() if rec_cap else None, out["hellos"].data_ptr() if hello_cap else None,
-                      out["snis"].data_ptr() if sni_cap else None, rec_cap, hello_cap, sni_cap)
-        _lib.check(_lib.lib().gpk_tls_batch(self.h, ctx.h, parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o),
-                                            _lib.stream_ptr(stream)))
-        return out
+        return self._decode(ctx, (data, offsets, caplens, records, layouts, parser), (rec_cap, hello_cap, sni_cap), None,
+                            out, stream)
 
     def decode_all(self, ctx, data, offsets, caplens, records, layouts, parser, rec_cap=0, hello_cap=0, sni_cap=0,
                    stream=None):
@@ -1342,36 +1326,21 @@ class TLSDecoder(_PostPass):
         the capacities given, and, when counts reports an overflow, a second
         one with exactly the sizes it needs. With the default capacities of 0
         the first call only sizes. Synchronizes on the counts."""
-        out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap,
-                          stream=stream)
-        counts = out["counts"].cpu().numpy().view("u4")
-        if int(counts[3]):
-            out = self.decode(ctx, data, offsets, caplens, records, layouts, parser, *self.needed(counts),
-                              stream=stream)
-        return out
+        return self._decode_all(ctx, (data, offsets, caplens, records, layouts, parser), (rec_cap, hello_cap, sni_cap),
+                                None, stream)
 
     @classmethod
     def decode_host(cls, data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap, fill=0):
         """The same over numpy arrays on the calling thread
         (gpk_tls_batch_host); `fill` is the byte the outputs start with."""
-        rec_cap, hello_cap, sni_cap = int(rec_cap), int(hello_cap), int(sni_cap)
-        out, b, r, _keep = cls._host_arguments(
-            data, offsets, caplens, records, layouts, fill,
-            (("recs", lambda n: rec_cap, _lib.TLS_REC_DTYPE), ("hellos", lambda n: hello_cap, _lib.TLS_HELLO_DTYPE),
-             ("snis", lambda n: sni_cap, "u1")))
-        o = _lib.Tlss(*[out[key].ctypes.data for key, _, _ in cls.OUTPUTS],
-                      out["recs"].ctypes.data if rec_cap else None, out["hellos"].ctypes.data if hello_cap else None,
-                      out["snis"].ctypes.data if sni_cap else None, rec_cap, hello_cap, sni_cap)
-        _lib.check(_lib.lib().gpk_tls_batch_host(parser.h, ctypes.byref(b), ctypes.byref(r), ctypes.byref(o)))
-        return out
+        return cls._decode_host((data, offsets, caplens, records, layouts, parser), (rec_cap, hello_cap, sni_cap), None,
+                                fill)
 
     @classmethod
     def decode_host_all(cls, data, offsets, caplens, records, layouts, parser, rec_cap=0, hello_cap=0, sni_cap=0):
         """decode_host with the retry of decode_all."""
-        out = cls.decode_host(data, offsets, caplens, records, layouts, parser, rec_cap, hello_cap, sni_cap)
-        if int(out["counts"][3]):
-            out = cls.decode_host(data, offsets, caplens, records, layouts, parser, *cls.needed(out["counts"]))
-        return out
+        return cls._decode_host_all((data, offsets, caplens, records, layouts, parser), (rec_cap, hello_cap, sni_cap),
+                                    None)
 
 
 class TLSStreamDecoder(_Handle):

@@ -1127,12 +1127,10 @@ class TunnelBatchResult:
         host = np.zeros((len(b.data) + 15) // 16 * 16 + 16, np.uint8)
         host[:len(b.data)] = b.data
         data = torch.from_numpy(host).to(dev)
-        det = Detunneler(max(len(b), 1), ctx.device) if kinds else None
-        ctd = ControlDecoder(max(len(b), 1), ctx.device) if self._ctl_kinds else None
-        ndd = NDPDecoder(max(len(b), 1), ctx.device) if self._ndp_kinds else None
-        dnd = DNSDecoder(max(len(b), 1), ctx.device) if self.parser._dns is not None else None
-        tld = TLSDecoder(max(len(b), 1), ctx.device) if self.parser._tls is not None else None
-        svd = ServiceDecoder(max(len(b), 1), ctx.device) if self._svc_kinds else None
+        det, ctd, ndd, dnd, tld, svd = (cls(max(len(b), 1), ctx.device) if wanted else None for cls, wanted in (
+            (Detunneler, kinds), (ControlDecoder, self._ctl_kinds), (NDPDecoder, self._ndp_kinds),
+            (DNSDecoder, self.parser._dns is not None), (TLSDecoder, self.parser._tls is not None),
+            (ServiceDecoder, self._svc_kinds)))
         try:
             work = [(int(self.parser.first), np.arange(len(b)), torch.from_numpy(b.offsets.view(np.int64)).to(dev),
                      torch.from_numpy(b.caplens.view(np.int32)).to(dev))]
@@ -1159,74 +1157,13 @@ class TunnelBatchResult:
                     r = dict(records=rec.cpu().numpy().view(_lib.RECORD_DTYPE),
                              err_args=err.cpu().numpy().view(np.uint32), flows=fl.cpu().numpy().view(np.uint64),
                              layouts=lay.cpu().numpy().view(_lib.LAYOUT_DTYPE))
-                    ctl = None
-                    if cout is not None:
-                        cm = int(cout["counts"][0].item())
-                        ctl = dict(verdict=cout["verdict"].cpu().numpy(),
-                                   class_start=cout["class_start"].cpu().numpy().view(np.uint32),
-                                   counts=cout["counts"].cpu().numpy().view(np.uint32),
-                                   index=cout["index"][:cm].cpu().numpy().view(np.uint32),
-                                   records=cout["records"][:cm * _lib.CONTROL_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.CONTROL_DTYPE))
-                    ndp = None
-                    if nout is not None:
-                        nc = nout["counts"].cpu().numpy().view(np.uint32)
-                        ndp = dict(verdict=nout["verdict"].cpu().numpy(),
-                                   class_start=nout["class_start"].cpu().numpy().view(np.uint32), counts=nc,
-                                   index=nout["index"][:int(nc[0])].cpu().numpy().view(np.uint32),
-                                   records=nout["records"][:int(nc[0]) * _lib.NDP_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.NDP_DTYPE),
-                                   entries=nout["entries"][:NDPDecoder.needed(nc) * _lib.NDP_ENTRY_DTYPE.itemsize]
-                                   .cpu().numpy().view(_lib.NDP_ENTRY_DTYPE))
-                    dns = None
-                    if dout is not None:
-                        dc = dout["counts"].cpu().numpy().view(np.uint32)
-                        need_rr, need_nb = DNSDecoder.needed(dc)
-                        dns = dict(verdict=dout["verdict"].cpu().numpy(),
-                                   class_start=dout["class_start"].cpu().numpy().view(np.uint32), counts=dc,
-                                   index=dout["index"][:int(dc[0])].cpu().numpy().view(np.uint32),
-                                   records=dout["records"][:int(dc[0]) * _lib.DNS_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.DNS_DTYPE),
-                                   rrs=dout["rrs"][:need_rr * _lib.DNS_RR_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.DNS_RR_DTYPE),
-                                   names=dout["names"][:need_nb].cpu().numpy())
-                    tls = None
-                    if tout is not None:
-                        tc = tout["counts"].cpu().numpy().view(np.uint32)
-                        need_rec, need_hello, need_sni = TLSDecoder.needed(tc)
-                        tls = dict(verdict=tout["verdict"].cpu().numpy(),
-                                   class_start=tout["class_start"].cpu().numpy().view(np.uint32), counts=tc,
-                                   index=tout["index"][:int(tc[0])].cpu().numpy().view(np.uint32),
-                                   records=tout["records"][:int(tc[0]) * _lib.TLS_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.TLS_DTYPE),
-                                   recs=tout["recs"][:need_rec * _lib.TLS_REC_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.TLS_REC_DTYPE),
-                                   hellos=tout["hellos"][:need_hello * _lib.TLS_HELLO_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.TLS_HELLO_DTYPE),
-                                   snis=tout["snis"][:need_sni].cpu().numpy())
-                    svc = None
-                    if sout is not None:
-                        sc = sout["counts"].cpu().numpy().view(np.uint32)
-                        svc = dict(verdict=sout["verdict"].cpu().numpy(),
-                                   class_start=sout["class_start"].cpu().numpy().view(np.uint32), counts=sc,
-                                   index=sout["index"][:int(sc[0])].cpu().numpy().view(np.uint32),
-                                   records=sout["records"][:int(sc[0]) * _lib.SVC_DTYPE.itemsize].cpu().numpy().view(
-                                       _lib.SVC_DTYPE),
-                                   entries=sout["entries"][:ServiceDecoder.needed(sc) * _lib.SVC_ENTRY_DTYPE.itemsize]
-                                   .cpu().numpy().view(_lib.SVC_ENTRY_DTYPE))
+                    ctl, ndp, dns, tls, svc = (None if o is None else d.to_host(o) for d, o in (
+                        (ctd, cout), (ndd, nout), (dnd, dout), (tld, tout), (svd, sout)))
                     if out is None:
                         self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
                                        caps.cpu().numpy().view(np.uint32), r, self._no_peel(n), ctl, dns, tls, ndp, svc)
                         continue
-                    m = int(out["counts"][0].item())
-                    pl = dict(verdict=out["verdict"].cpu().numpy(),
-                              class_start=out["class_start"].cpu().numpy().view(np.uint32),
-                              counts=out["counts"].cpu().numpy().view(np.uint32),
-                              index=out["index"][:m].cpu().numpy().view(np.uint32),
-                              in_offsets=out["in_offsets"][:m].cpu().numpy().view(np.uint64),
-                              in_caplens=out["in_caplens"][:m].cpu().numpy().view(np.uint32),
-                              tunnels=out["tunnels"][:m * _lib.TUNNEL_DTYPE.itemsize].cpu().numpy().view(
-                                  _lib.TUNNEL_DTYPE))
+                    pl = det.to_host(out)
                     part = self._add_part(level, first, index, offs.cpu().numpy().view(np.uint64),
                                           caps.cpu().numpy().view(np.uint32), r, pl, ctl, dns, tls, ndp, svc)
                     for lt, js in self._next_work(part, level):
